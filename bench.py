@@ -21,7 +21,10 @@ the backbone of step i + 1 (ImageTower.detect(overlap_post=True); --no-overlap-p
 kernel of a step on one stream).  Every step's post-process completes inside the timed bracket —
 the closing torch.cuda.synchronize() drains both streams.
 
-Prints ONE JSON line (rank 0) with the driver's contract plus:
+Prints ONE JSON line (rank 0) with the driver's contract (metric, value, unit, n_gpus, steps, warmup, ms_per_step,
+higher_is_better, dtype, config; at N > 1 also per_rank below).  A plain run does only that: set-up, warm-up, the
+timed steps, the line.  --dump-outputs DIR also writes what the last timed step returned (write_outputs).
+--full adds the side measurements, all after the timed steps (retrieval mode: its cpu_baseline):
   roofline      — the dominant kernel (the GEMM that runs the ConvNeXt MLPs: fp16x3 direct-to-LDS, or fp32 MFMA),
                   algorithmic flops / HIP-event time of its launches inside the timed region (events stamped by the
                   kernels' own dispatches, on the last two timed steps: see GemmTimer)
@@ -32,6 +35,8 @@ Prints ONE JSON line (rank 0) with the driver's contract plus:
   host_fed      — (N = 1) the same step fed from PINNED HOST memory: the uint8 batch is uploaded every step and the
                   <= 300-row results (boxes, scores, labels, counts) are copied back, both on a copy stream that
                   overlaps the next / previous step's compute; never the headline `value`
+  other_configs — (N = 1, the default configuration) short runs of configs[2] / [3] / [4]
+and, with or without --full:
   per_rank      — (N > 1) every rank's own ms/step and how long its stream stalled on the region gather
 """
 import argparse
@@ -148,7 +153,7 @@ def parse():
                          "retrieval: the object-retrieval scoring step of configs[4] — 300 kept regions per image against a "
                          "1M-class bank, class-sharded over the ranks (retrieval_metric.py:367-377)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the short legs of configs[2] / [3] / [4] that the default line carries in `other_configs` (N = 1 only)")
+                    help="skip the short legs of configs[2] / [3] / [4] that the --full line carries in `other_configs` (N = 1 only)")
     ap.add_argument("--precision", choices=["fp32", "fp16x3"], default=None,
                     help="arithmetic of the dense convs/linears (default: wedetect_amd.engine.DEFAULT_PRECISION); "
                          "fp16x3 = fp32 operands split into fp16 hi+lo, three MFMA passes, fp32 accumulate")
@@ -164,7 +169,15 @@ def parse():
     ap.add_argument("--no-calibrate", action="store_true",
                     help="skip the untimed range-calibration pass (an fp32 run of the tower): keeps it out of a rocprofv3 trace")
     ap.add_argument("--cpu-runs", type=int, default=5, help="timed CPU-oracle passes per leg (median reported; 3 warm-ups)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: per-kernel figures (roofline, gemm_kernels, sim_gemm, from the serial "
+                         "leg), fp32_mode, host_fed, other_configs, cpu_baseline.  Off: set-up, warm-up, the timed steps, the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32 / float64, "
+                         "<= 64 MB in all; the inputs are seeded, so two builds can be compared output for output)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if a.classes is None:
         a.classes = 1_000_000 if a.mode == "retrieval" else 80
     return a
@@ -565,7 +578,7 @@ def fp32_sim_reference(tower, L, text, normalize, reps=5):
 
 
 def detect_leg(timer, L, arch, B, K, uni, steps=20, warmup=3):
-    """A short run of ANOTHER BASELINE configuration inside the default invocation (configs[2] / [3] were
+    """A short run of ANOTHER BASELINE configuration inside a --full invocation (configs[2] / [3] were
     builder-run files only): same protocol as the headline — calibration, ``warmup`` untimed steps, ``steps`` timed steps
     issued back to back with the post-process on the second stream, wall clock around a full drain — and the per-launch
     GEMM timing on the last step for the similarity GEMM's fraction."""
@@ -731,6 +744,7 @@ def retrieval_leg(L, n_img, regions, K, rank, world, steps, warmup, dist=None):
         except Exception:
             traffic, traffic_src = None, None
     return dict(dt=dt, precision=scorer.precision, tripped=scorer.tripped(), checksum=float(out[:, :: max(1, K // 4096)].double().sum().item()),
+                scores=out,
                 roofline={"kernel": ("split_gemm_p8_kernel<retrieval: bank rows x region rows, fp16x3 256x256x32/8w, in-register max over "
                                      "regions + one sigmoid per (image, class)> (3 x v_mfma_f32_32x32x16_f16 per product)"
                                      if scorer.precision == "fp16x3" else "retrieval_max_kernel (fp32 MFMA 16x16x4)"),
@@ -769,6 +783,43 @@ def retrieval_cpu_baseline(regions, K, sample_images=2, sample_classes=100_000):
     return dict(value=round(sample_classes / K / per_img, 5), unit="images/s", cores=torch.get_num_threads(), kind="port",
                 sample=f"oracle/postprocess.py retrieval_scores (torch fp32 einsum + sigmoid + max) on {sample_images} images x {regions} "
                        f"regions x {sample_classes} classes: {per_img:.3f} s per image; value = that rate scaled to {K} classes (linear in K)")
+
+
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+def write_outputs(out_dir: str, arrays) -> None:
+    """--dump-outputs: ``arrays`` (name -> tensor / array, what the last timed step returned) as ``out_dir/<name>.npy``,
+    floats as float32 / float64, integers as float64 (exact).  Arrays that do not fit the 64 MB budget left by the smaller
+    ones keep a fixed, seeded sample of rows along their longest axis; ``<name>_sample_index.npy`` then holds those rows."""
+    arrays = {k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)) for k, v in arrays.items()}
+    arrays = {k: (v if v.dtype in (np.float32, np.float64) else v.astype(np.float64)) for k, v in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    left = DUMP_BUDGET_BYTES - 2 * 4096 * len(arrays)          # room for the .npy headers of up to two files per array
+    for i, (name, a) in enumerate(sorted(arrays.items(), key=lambda kv: kv[1].nbytes)):
+        share = left // (len(arrays) - i)
+        if a.nbytes > share:
+            axis = int(np.argmax(a.shape))
+            keep = max(1, share // (a.nbytes // a.shape[axis] + 8))           # rows of the sample + their float64 index
+            idx = np.sort(np.random.default_rng(0).choice(a.shape[axis], keep, replace=False))
+            a = np.take(a, idx, axis=axis)
+            np.save(os.path.join(out_dir, f"{name}_sample_index.npy"), idx.astype(np.float64))
+            left -= idx.size * 8
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a))
+        left -= a.nbytes
+
+
+def detect_outputs(res) -> dict:
+    """The caller's view of one detect step: rows [0, count) of every image; the rows past an image's count are stale buffer
+    contents (never cleared) and are written as zeros, so that two runs compare equal where their results do."""
+    n = res["count"].to(torch.int64).clamp(min=0)
+    out = {"count": res["count"]}
+    for k in ("bboxes", "scores", "labels", "anchors", "embeddings"):
+        if k in res:
+            v = res[k]
+            live = torch.arange(v.shape[1], device=v.device)[None, :] < n[:, None]
+            out[k] = torch.where(live.view(*live.shape, *([1] * (v.dim() - 2))), v, torch.zeros((), dtype=v.dtype, device=v.device))
+    return out
 
 
 def launch_ranks(n: int) -> int:
@@ -887,7 +938,9 @@ def main():
                    "roofline": r["roofline"]}
             if dist_on:
                 out["ranks_seen"], out["collective_backend"] = ranks_seen, backend_name
-            if world == 1 and not args.no_cpu_baseline:
+            if args.dump_outputs:
+                write_outputs(args.dump_outputs, {"scores": r["scores"]})
+            if args.full and world == 1 and not args.no_cpu_baseline:
                 dog.phase("cpu baseline")
                 out["cpu_baseline"] = retrieval_cpu_baseline(args.regions, K)
             print(json.dumps(out), file=json_out, flush=True)
@@ -906,8 +959,10 @@ def main():
     uni = args.mode == "uni"
     if not uni:
         meta[:, 7] = 1.0                    # mmdet order: rescale before NMS
+    full = args.full
     timer = GemmTimer(L)
-    timer.install()
+    if full:
+        timer.install()                     # per-launch stamps on the last timed steps: --full only (a plain run times bare steps)
 
     gatherer = RegionGatherer(timeout_s=dog.timeout_s) if dist_on else None
     lvl_scale = torch.tensor(tower.lvl_logit_scale, dtype=torch.float32, device="cuda")
@@ -956,19 +1011,23 @@ def main():
     # per-launch kernel timing covers the LAST n_inst steps of the timed region only: stamping every launch costs the
     # step ~1.2 ms (2.4 %: scripts/step_timer_overhead.py), so the headline would otherwise measure its own probe
     n_inst = min(args.steps, 1 if args.steps < 4 else 2)
-    timer.prepare(timer.count // max(1, args.warmup) * n_inst)
+    if full:
+        timer.prepare(timer.count // max(1, args.warmup) * n_inst)
     timer.mode = "off"
-    clock = ClockSampler(local)
-    clock.start()
+    clock = ClockSampler(local) if full else None
+    if clock is not None:
+        clock.start()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        if i == args.steps - n_inst:
+        if full and i == args.steps - n_inst:
             timer.mode = "time"
         res = step(measure_stall=dist_on)
     sync()
     dt = time.perf_counter() - t0
-    clk = clock.stop()
+    clk = clock.stop() if clock is not None else None
     timer.mode = "off"
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, detect_outputs(res))      # before the serial leg of --full reuses the buffers
     per_rank = None
     ranks_seen, backend_name = 1, None
     dog.phase("closing collectives")
@@ -994,7 +1053,7 @@ def main():
     # region's own stamps are kept beside them (roofline.timed_region).
     concurrent = overlap and (tower._n_chains() > 1 or tower._pipe_neck_on())
     timed_summ = None
-    if concurrent:
+    if full and concurrent:
         dog.phase("serial leg (per-kernel timing)")
         timed_summ = timer.summary(busy=True) if rank == 0 else None
         saved_modes = (tower.bb_chains, tower.pipe_neck, tower.force_tile_forms)
@@ -1012,20 +1071,21 @@ def main():
         tower.bb_chains, tower.pipe_neck, tower.force_tile_forms = saved_modes
 
     if rank == 0:
-        summ = timer.summary()
-        dom_tag = max(summ, key=lambda k: summ[k]["flops_total"])
-        dom = summ[dom_tag]
-        flops_img = sum(v["flops_total"] for v in summ.values()) / (n_inst * B)
-        dom_split = dom_tag.startswith("fp16x3")
-        # fp16x3 issues three fp16 MFMA passes per fp32-accurate product: the roof for ALGORITHMIC
-        # flops is the fp16 dense peak / 3; the fraction of the raw fp16 peak is reported beside it.
-        dom_peak = round(F16_MFMA_PEAK_TFLOPS / SPLIT_PASSES, 1) if dom_split else F32_MFMA_PEAK_TFLOPS
-        dom_fn = ("split_gemm_p8" if "/p8" in dom_tag else "split_gemm_p4" if "/p4" in dom_tag else "split_gemm_glds" if "glds" in dom_tag
-                  else "split_gemm_pingpong" if "pingpong" in dom_tag else "split_gemm")
-        dom_kernel = (f"{dom_fn}_kernel<{dom_tag}> (3 x v_mfma_f32_32x32x16_f16 per product)" if dom_split
-                      else f"conv_gemm_kernel<{dom_tag}> (fp32 MFMA 16x16x4)")
-        traffic, traffic_src = (measured_traffic(dom_tag) if (B, S, K, args.arch, args.mode) == (32, 640, 80, "base", "detect")
-                                else (None, None))
+        if full:
+            summ = timer.summary()
+            dom_tag = max(summ, key=lambda k: summ[k]["flops_total"])
+            dom = summ[dom_tag]
+            flops_img = sum(v["flops_total"] for v in summ.values()) / (n_inst * B)
+            dom_split = dom_tag.startswith("fp16x3")
+            # fp16x3 issues three fp16 MFMA passes per fp32-accurate product: the roof for ALGORITHMIC
+            # flops is the fp16 dense peak / 3; the fraction of the raw fp16 peak is reported beside it.
+            dom_peak = round(F16_MFMA_PEAK_TFLOPS / SPLIT_PASSES, 1) if dom_split else F32_MFMA_PEAK_TFLOPS
+            dom_fn = ("split_gemm_p8" if "/p8" in dom_tag else "split_gemm_p4" if "/p4" in dom_tag else "split_gemm_glds" if "glds" in dom_tag
+                      else "split_gemm_pingpong" if "pingpong" in dom_tag else "split_gemm")
+            dom_kernel = (f"{dom_fn}_kernel<{dom_tag}> (3 x v_mfma_f32_32x32x16_f16 per product)" if dom_split
+                          else f"conv_gemm_kernel<{dom_tag}> (fp32 MFMA 16x16x4)")
+            traffic, traffic_src = (measured_traffic(dom_tag) if (B, S, K, args.arch, args.mode) == (32, 640, 80, "base", "detect")
+                                    else (None, None))
         out = {
             "metric": f"images/s at {S}x{S} (WeDetect-{args.arch.capitalize()} image tower + {K}-class similarity + top-k/NMS)",
             "value": round(world * B * args.steps / dt, 3),
@@ -1059,8 +1119,8 @@ def main():
                            "(tests/test_gpu_precision.py); --precision fp32 runs native fp32 MFMA"} if split else {}),
                        "kept_regions_last_step_rank0": kept, "fp16x3_range_guard_tripped": overflow,
                        "fp16x3_trips": int(tower.fp16x3_trips) + int(overflow),      # ImageTower's counter (checked_counts) + this run's raw flags
-                       "gemm_gflop_per_image": round(flops_img / 1e9, 2)},
-            "roofline": {"kernel": dom_kernel, "bound": "mfma",
+                       **({"gemm_gflop_per_image": round(flops_img / 1e9, 2)} if full else {})},
+            **({"roofline": {"kernel": dom_kernel, "bound": "mfma",
                          "achieved": round(dom["tflops"], 2), "peak": dom_peak, "unit": "TFLOP/s",
                          "frac": round(dom["tflops"] / dom_peak, 4),
                          **({"effective_mhz": clk["mean_mhz"], "effective_mhz_min_max": [clk["min_mhz"], clk["max_mhz"]],
@@ -1087,38 +1147,39 @@ def main():
                                             "in the timed region launches of several streams share the chip (timed_region below)",
                              "timed_region": timed_region_record(timed_summ, dom_tag, dom_peak, n_inst, tower)} if concurrent else {})},
             "gemm_kernels": {k: {"launches_per_step": v["launches"] // n_inst, "avg_us": round(v["avg_us"], 2),
-                                 "tflops": round(v["tflops"], 2)} for k, v in sorted(summ.items())},
+                                 "tflops": round(v["tflops"], 2)} for k, v in sorted(summ.items())}} if full else {}),
         }
-        simrec = sim_record(summ, L, B * tower.ntot, K)
-        if simrec is not None:
-            out["sim_gemm"] = simrec
-            if simrec["dtype"] == "fp16x3":                   # a bank of >= 256 rows: keep the fp32-MFMA figure beside it
-                out["sim_gemm"]["fp32_kernel"] = fp32_sim_reference(tower, L, text, not uni)
-        dog.phase("side legs (fp32 reference, host-fed, other configurations, cpu baseline)")
-        dog.timeout_s = max(dog.timeout_s, 900.0)
-        if world == 1 and split and not args.no_fp32_reference:
-            # the same workload with native fp32 MFMA arithmetic, measured in this run (same images, weights, bank)
-            out["fp32_mode"] = fp32_reference_run(args, tower, images, text, meta, uni)
-        if world == 1 and not args.no_host_fed:
-            out["host_fed"] = host_fed_run(tower, images, text, meta, uni, min(args.steps, 20))
         if per_rank is not None:
             out["per_rank"] = per_rank
             out["ranks_seen"] = ranks_seen          # all_reduce(1) over the job's process group: the collective library saw this many
             out["collective_backend"] = backend_name
-        if (world == 1 and split and not args.no_other_configs
-                and (B, S, K, args.arch, args.mode) == (32, 640, 80, "base", "detect")):
-            # configs[2], [3] (one rank's share) and [4] (per-GPU form, whole bank) in the driver's one line: twenty timed steps (configs[4]: five)
-            # each after two warm-ups, same protocol as the headline
-            other = {}
-            other["configs[2] large_b16_k1203"] = detect_leg(timer, L, "large", 16, 1203, uni=False)
-            other["configs[3] base_uni_b32_k256 (one rank's step; the exchange is the --gpus N path)"] = detect_leg(timer, L, "base", 32, 256, uni=True)
-            r = retrieval_leg(L, 32, 300, 1_000_000, 0, 1, steps=5, warmup=2)
-            other["configs[4] retrieval_1m_classes (per-GPU form: 32 images x 300 regions, whole bank)"] = {
-                "value": round(32 * 5 / r["dt"], 3), "unit": "images/s", "ms_per_step": round(1e3 * r["dt"] / 5, 3), "steps": 5, "warmup": 2,
-                "precision": r["precision"], "fp16x3_range_guard_tripped": r["tripped"], "roofline": r["roofline"]}
-            out["other_configs"] = other
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(args.arch, S, K, args.cpu_runs)
+        if full:
+            simrec = sim_record(summ, L, B * tower.ntot, K)
+            if simrec is not None:
+                out["sim_gemm"] = simrec
+                if simrec["dtype"] == "fp16x3":                   # a bank of >= 256 rows: keep the fp32-MFMA figure beside it
+                    out["sim_gemm"]["fp32_kernel"] = fp32_sim_reference(tower, L, text, not uni)
+            dog.phase("side legs (fp32 reference, host-fed, other configurations, cpu baseline)")
+            dog.timeout_s = max(dog.timeout_s, 900.0)
+            if world == 1 and split and not args.no_fp32_reference:
+                # the same workload with native fp32 MFMA arithmetic, measured in this run (same images, weights, bank)
+                out["fp32_mode"] = fp32_reference_run(args, tower, images, text, meta, uni)
+            if world == 1 and not args.no_host_fed:
+                out["host_fed"] = host_fed_run(tower, images, text, meta, uni, min(args.steps, 20))
+            if (world == 1 and split and not args.no_other_configs
+                    and (B, S, K, args.arch, args.mode) == (32, 640, 80, "base", "detect")):
+                # configs[2], [3] (one rank's share) and [4] (per-GPU form, whole bank) in the driver's one line: twenty timed steps (configs[4]: five)
+                # each after two warm-ups, same protocol as the headline
+                other = {}
+                other["configs[2] large_b16_k1203"] = detect_leg(timer, L, "large", 16, 1203, uni=False)
+                other["configs[3] base_uni_b32_k256 (one rank's step; the exchange is the --gpus N path)"] = detect_leg(timer, L, "base", 32, 256, uni=True)
+                r = retrieval_leg(L, 32, 300, 1_000_000, 0, 1, steps=5, warmup=2)
+                other["configs[4] retrieval_1m_classes (per-GPU form: 32 images x 300 regions, whole bank)"] = {
+                    "value": round(32 * 5 / r["dt"], 3), "unit": "images/s", "ms_per_step": round(1e3 * r["dt"] / 5, 3), "steps": 5, "warmup": 2,
+                    "precision": r["precision"], "fp16x3_range_guard_tripped": r["tripped"], "roofline": r["roofline"]}
+                out["other_configs"] = other
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(args.arch, S, K, args.cpu_runs)
         print(json.dumps(out), file=json_out, flush=True)
     if dist is not None:
         dog.phase("final barrier")

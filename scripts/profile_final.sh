@@ -12,7 +12,7 @@ mkdir -p $OUT
 # pipelined form launches of several streams share the chip and a launch's duration / counters are not its own.  The default
 # command gets a kernel trace of its own (summary_pipelined.txt): the whole picture, half-batch launches of the two image chains.
 export WEDETECT_BB_CHAINS=1 WEDETECT_PIPE_NECK=0 WEDETECT_FORCE_TILE=1
-CMD="python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-fp32-reference --no-host-fed --no-other-configs --no-calibrate $*"
+CMD="python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-fp32-reference --no-host-fed --no-other-configs --no-calibrate $*"
 timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/trace -o p -- $CMD > $OUT/trace_bench.json 2> $OUT/trace.err
 if [ -n "$TRACE_ONLY" ]; then     # kernel trace only (TRACE_ONLY=1): no counter passes
   python scripts/rocpd_summary.py $(ls $OUT/trace/*.db | head -1) > $OUT/summary.txt 2>&1

@@ -3,7 +3,7 @@ set -u
 STEP=${1:-baseline}; shift || true
 OUT=gpurun_out/r06/$STEP; mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
-Q="--steps 30 --warmup 8 --no-cpu-baseline --no-fp32-reference --no-host-fed --no-other-configs"
+Q="--full --steps 30 --warmup 8 --no-cpu-baseline --no-fp32-reference --no-host-fed --no-other-configs"
 line() { python - "$@" <<'PY'
 import json,sys
 for f in sys.argv[1:]:
@@ -219,7 +219,7 @@ chains)
   cat $OUT/tests.log; line $OUT/bench_*.json; tail -n 3 $OUT/*.err | tail -n 30
   ;;
 baseline)
-  python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+  python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
   WEDETECT_DAG=0 python bench.py $Q > $OUT/bench_dag0.json 2> $OUT/bench_dag0.err
   OUT=$OUT/layers.json python scripts/neck_layer_times.py > $OUT/layers.txt 2>&1
   line $OUT/bench_default.json $OUT/bench_dag0.json
@@ -311,7 +311,7 @@ smallb)
   python bench.py $Q --batch 8 > $OUT/bench_b8.json 2> $OUT/bench_b8.err
   WEDETECT_SPLIT_K=1 python bench.py $Q --batch 1 > $OUT/bench_b1_splitk.json 2> $OUT/bench_b1_splitk.err
   WEDETECT_SPLIT_K=1 python bench.py $Q --batch 8 > $OUT/bench_b8_splitk.json 2> $OUT/bench_b8_splitk.err
-  timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/trace -o p -- python bench.py --steps 20 --warmup 5 --batch 1 --no-cpu-baseline --no-fp32-reference --no-host-fed --no-other-configs > /dev/null 2> $OUT/trace.err
+  timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/trace -o p -- python bench.py --full --steps 20 --warmup 5 --batch 1 --no-cpu-baseline --no-fp32-reference --no-host-fed --no-other-configs > /dev/null 2> $OUT/trace.err
   python scripts/rocpd_summary.py $(ls $OUT/trace/*.db | head -1) > $OUT/summary_b1.txt 2>&1
   rm -rf $OUT/trace
   line $OUT/bench_b*.json; head -40 $OUT/summary_b1.txt | cut -c1-120; grep "total" $OUT/layers_b1.txt $OUT/layers_b8.txt
@@ -356,8 +356,8 @@ ceiling)
   ;;
 dryrun)
   # the N > 1 code of bench.py with 8 / 2 gloo ranks time-sliced on the one GPU of this pool (not a scaling measurement)
-  WEDETECT_BENCH_SHARE_GPU=1 WEDETECT_BENCH_BACKEND=gloo timeout 900 python bench.py --gpus 8 --batch 4 --steps 3 --warmup 1 --no-cpu-baseline --no-fp32-reference --no-host-fed --no-other-configs > $OUT/bench_n8_dry.json 2> $OUT/bench_n8_dry.err
-  WEDETECT_BENCH_SHARE_GPU=1 WEDETECT_BENCH_BACKEND=gloo timeout 900 python bench.py --gpus 2 --batch 32 --steps 3 --warmup 1 --no-cpu-baseline --no-fp32-reference --no-host-fed --no-other-configs > $OUT/bench_n2_dry.json 2> $OUT/bench_n2_dry.err
+  WEDETECT_BENCH_SHARE_GPU=1 WEDETECT_BENCH_BACKEND=gloo timeout 900 python bench.py --full --gpus 8 --batch 4 --steps 3 --warmup 1 --no-cpu-baseline --no-fp32-reference --no-host-fed --no-other-configs > $OUT/bench_n8_dry.json 2> $OUT/bench_n8_dry.err
+  WEDETECT_BENCH_SHARE_GPU=1 WEDETECT_BENCH_BACKEND=gloo timeout 900 python bench.py --full --gpus 2 --batch 32 --steps 3 --warmup 1 --no-cpu-baseline --no-fp32-reference --no-host-fed --no-other-configs > $OUT/bench_n2_dry.json 2> $OUT/bench_n2_dry.err
   WEDETECT_BENCH_SHARE_GPU=1 WEDETECT_BENCH_BACKEND=gloo timeout 900 python bench.py --gpus 2 --mode retrieval --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_n2_retrieval_dry.json 2> $OUT/bench_n2_retrieval_dry.err
   for f in $OUT/bench_n*_dry.json; do python -c "
 import json; d=json.loads(open('$f').read().strip().splitlines()[-1]); print('$f'.split('/')[-1], d['n_gpus'], d.get('ranks_seen'), d.get('collective_backend'), d['value'], d['unit'])" || tail -n 5 ${f%.json}.err; done

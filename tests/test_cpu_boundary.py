@@ -569,6 +569,41 @@ def test_bench_gpus_n_launches_n_ranks_itself(monkeypatch, capsys):
     assert "WORLD_SIZE 2" in str(e.value.code)
 
 
+def test_bench_full_and_dump_options(monkeypatch, tmp_path):
+    """--full (side measurements) is off by default, --steps is the timed-step count (>= 1), and --dump-outputs writes the
+    caller's view of the last step: floats as float32 / float64, integers as float64, rows past an image's count zeroed,
+    arrays over the 64 MB budget as a seeded sample of rows."""
+    import importlib
+    import sys
+    bench = importlib.import_module("bench")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7"])
+    a = bench.parse()
+    assert a.steps == 7 and not a.full and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", str(tmp_path / "d")])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == str(tmp_path / "d")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+    g = torch.Generator().manual_seed(3)
+    res = dict(bboxes=torch.randn(3, 5, 4, generator=g), scores=torch.rand(3, 5, generator=g),
+               labels=torch.arange(15, dtype=torch.int32).view(3, 5), anchors=torch.arange(15, dtype=torch.int32).view(3, 5),
+               count=torch.tensor([2, 0, -1], dtype=torch.int32), embeddings=torch.randn(3, 5, 768, generator=g))
+    bench.write_outputs(str(tmp_path / "d"), bench.detect_outputs(res))
+    got = {f[:-4]: np.load(tmp_path / "d" / f) for f in os.listdir(tmp_path / "d")}
+    assert sorted(got) == ["anchors", "bboxes", "count", "embeddings", "labels", "scores"]
+    assert got["labels"].dtype == np.float64 and got["embeddings"].dtype == np.float32
+    assert np.array_equal(got["embeddings"][0, :2], res["embeddings"][0, :2].numpy()) and not got["embeddings"][0, 2:].any()
+    assert not got["labels"][1:].any() and np.array_equal(got["labels"][0], [0, 1, 0, 0, 0])
+    big = torch.randn(2, 9_000_000, generator=g)                              # 72 MB: over the budget
+    for d in ("b1", "b2"):
+        bench.write_outputs(str(tmp_path / d), {"scores": big})
+    idx = np.load(tmp_path / "b1" / "scores_sample_index.npy").astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "b1" / "scores.npy"), big.numpy()[:, idx])
+    assert np.array_equal(idx, np.load(tmp_path / "b2" / "scores_sample_index.npy"))
+    assert sum(os.path.getsize(tmp_path / "b1" / f) for f in os.listdir(tmp_path / "b1")) <= 64_000_000
+
+
 def test_bench_busy_time_is_the_union_of_launch_intervals():
     """Round 6: launches of one kernel family on different streams overlap (image chains; the previous step's neck beside the
     next backbone) — bench.py reports the family's flops over the time AT LEAST ONE launch was running (roofline.timed_region)."""

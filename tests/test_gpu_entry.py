@@ -334,7 +334,7 @@ def test_bench_collectives_on_rccl_with_one_rank(mode):
     import sys
     env = dict(os.environ, WEDETECT_BENCH_FORCE_DIST="1", WORLD_SIZE="1", RANK="0", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1",
                MASTER_PORT="29547", WEDETECT_BENCH_TIMEOUT="240", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"]
     if mode == "detect":
         cmd += ["--batch", "4", "--no-fp32-reference", "--no-host-fed", "--no-other-configs"]
     else:
@@ -350,3 +350,34 @@ def test_bench_collectives_on_rccl_with_one_rank(mode):
     if mode == "detect":
         assert out["per_rank"][0]["rank"] == 0 and out["per_rank"][0]["gather_handover_ms_per_step"] >= 0.0
         assert "all-gather" not in out["config"]["parallelism"]               # the line still describes a one-GPU job
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain `bench.py` run (no --full): the headline line and nothing that takes runs of its own; --dump-outputs writes what
+    the last timed step returned, and a second process with the same arguments writes the same arrays bit for bit."""
+    import subprocess
+    import sys
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--arch", "tiny", "--batch", "2", "--size", "128",
+           "--steps", "3", "--warmup", "1"]
+    outs = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        p = subprocess.run(cmd + ["--dump-outputs", str(d)], capture_output=True, text=True, timeout=300)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = p.stdout.splitlines()
+        assert len(lines) == 1, p.stdout[-2000:]
+        line = json.loads(lines[0])
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert line["unit"] == "images/s" and line["higher_is_better"] is True and line["dtype"]
+        for side in ("roofline", "gemm_kernels", "sim_gemm", "fp32_mode", "host_fed", "other_configs", "cpu_baseline"):
+            assert side not in line, side
+        outs.append({f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))})
+    a, b = outs
+    assert sorted(a) == ["anchors", "bboxes", "count", "embeddings", "labels", "scores"], sorted(a)
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    n = a["count"].astype(np.int64)
+    assert a["embeddings"].shape == (2, a["scores"].shape[1], 768) and (n >= 0).all() and n.sum() > 0
+    for i, k in enumerate(n):
+        assert (a["scores"][i, k:] == 0).all() and (a["embeddings"][i, k:] == 0).all()       # rows past the count are zeroed
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
