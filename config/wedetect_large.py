@@ -17,3 +17,9 @@ test_pipeline = [
     dict(type="PackDetInputs",
          meta_keys=("img_id", "img_path", "ori_shape", "img_shape", "scale_factor", "pad_param", "texts")),
 ]
+# the evaluation datasets of the base file run this pipeline (1280 x 1280)
+coco_val_dataset = dict(pipeline=test_pipeline)
+lvis_minival_dataset = dict(pipeline=test_pipeline)
+lvis_od_val_dataset = dict(pipeline=test_pipeline)
+val_dataloader = dict(dataset=coco_val_dataset)
+test_dataloader = val_dataloader

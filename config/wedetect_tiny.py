@@ -1,7 +1,9 @@
-# WeDetect-Tiny, inference view.  Evaluates to the same `model`, `img_scale` and `test_pipeline` as the reference's
-# config/wedetect_tiny.py (checked by tests/test_cpu.py against tests/golden/model_cfgs.json); the training,
-# dataset and evaluator sections of that file are outside this repository's scope, and a reference config file can
-# be used here unchanged (wedetect_amd.cfgfile.Config reads it).
+# WeDetect-Tiny, inference and evaluation view.  Evaluates to the same `model`, `img_scale` and `test_pipeline` as the
+# reference's config/wedetect_tiny.py (checked by tests/test_cpu.py against tests/golden/model_cfgs.json), and carries
+# its test datasets and evaluators (COCO val2017, LVIS minival / od-val) with the same keys and values, for test.py.
+# The training sections of that file are outside this repository's scope, and a reference config file can be used
+# here unchanged (wedetect_amd.cfgfile.Config reads it).  The class-text JSON files (data/texts/) are data: bring your
+# own, as with checkpoints.
 _base_ = ["default_runtime.py"]
 
 size = "tiny"
@@ -53,3 +55,46 @@ test_pipeline = [
     dict(type="PackDetInputs",
          meta_keys=("img_id", "img_path", "ori_shape", "img_shape", "scale_factor", "pad_param", "texts")),
 ]
+
+# ------------------------------------------------------------------------------------------ evaluation (test.py)
+# Images are read in annotation-file order; label k is the k-th category in ascending id order.
+coco_val_dataset = dict(
+    type="MultiModalDataset",
+    dataset=dict(type="WeCocoDataset", data_root="data/coco/", test_mode=True,
+                 ann_file="data/coco/annotations/instances_val2017.json", data_prefix=dict(img="val2017"),
+                 batch_shapes_cfg=None),
+    class_text_path="data/texts/coco_zh_class_texts.json",
+    pipeline=test_pipeline)
+
+lvis_minival_dataset = dict(
+    type="MultiModalDataset",
+    dataset=dict(type="YOLOv5LVISV1Dataset", data_root="data/coco/", test_mode=True,
+                 ann_file="data/lvis/lvis_v1_minival_inserted_image_name.json", data_prefix=dict(img=""),
+                 batch_shapes_cfg=None),
+    class_text_path="data/texts/lvis_v1_zh_class_texts.json",
+    pipeline=test_pipeline)
+
+lvis_od_val_dataset = dict(
+    type="MultiModalDataset",
+    dataset=dict(type="YOLOv5LVISV1Dataset", data_root="data/coco/", test_mode=True,
+                 ann_file="data/lvis/lvis_od_val.json", data_prefix=dict(img=""), batch_shapes_cfg=None),
+    class_text_path="data/texts/lvis_v1_zh_class_texts.json",
+    pipeline=test_pipeline)
+
+# box mAP on the device (wedetect_amd.det_eval)
+coco_evaluator = dict(type="CocoMetric", ann_file="data/coco/annotations/instances_val2017.json", metric="bbox")
+lvis_minival_evaluator = dict(type="LVISMetric", ann_file="data/lvis/lvis_v1_minival_inserted_image_name.json",
+                              metric="bbox")
+lvis_od_val_evaluator = dict(type="LVISMetric", ann_file="data/lvis/lvis_od_val.json", metric="bbox")
+
+# batch_size > 1 may change predictions in the last bits (latency split-K of small batches)
+val_dataloader = dict(batch_size=1, num_workers=2, persistent_workers=True, pin_memory=True, drop_last=False,
+                      sampler=dict(type="DefaultSampler", shuffle=False), dataset=coco_val_dataset)
+test_dataloader = val_dataloader
+
+# LVIS: val_evaluator = lvis_minival_evaluator (or lvis_od_val_evaluator), with the matching dataset above
+val_evaluator = coco_evaluator
+test_evaluator = val_evaluator
+
+val_cfg = dict(type="ValLoop")
+test_cfg = dict(type="TestLoop")

@@ -346,6 +346,47 @@ int wd_recall_match(const float* gts, const int32_t* gt_off, const float* props,
                     const int32_t* budgets, int32_t n_budget, float* scratch, int64_t scratch_floats_per_block, float* out,
                     int32_t total_gt, int32_t legacy, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * COCO / LVIS box mAP on the device (wedetect_amd/det_eval.py; rules: that module's docstring).
+ * wd_det_match — one wave per (image, category) pair p, pairs ordered (category, image position):
+ * dets [pair_det_off[p], +1) (xyxy fp32, scores, det_flag bit 0 = category not exhaustively annotated),
+ * gts [pair_gt_off[p], +1) (xywh and JSON area in float64, gt_flag bit 0 ignore, bit 1 crowd, bit 2 id != 0).
+ * The dets are ranked by score (stable) and the first pair_slot_off[p+1] - pair_slot_off[p] = min(D, max_det)
+ * are matched greedily at the 10 iou_thr (already min(t, 1 - 1e-10)) x 4 area_rng [lo, hi] pairs.  Writes per
+ * slot s: slot_score, slot_rank and sort_keys[s] = {(u64)pair_cat << 32 | ~ordered(score), s} (-0.0 keyed as
+ * +0.0); per lane
+ * l = a * 10 + t: flags[l * n_slot + s] (bit 0 matched to a gt of nonzero id, bit 1 ignored); npig[p * 4 + a]
+ * = gts kept in range a.  Pair workspace: wd_det_match_workspace_bytes(kept dets, gts) bytes; pairs whose
+ * workspace exceeds wd_det_match_lds_bytes() need pair_scratch[p] = a byte offset into scratch (16-aligned),
+ * the others pair_scratch[p] = -1.  *err (zeroed by the caller) gets a nonzero bit when a pair's layout is
+ * inconsistent (that pair is skipped). */
+typedef struct WdDetSortKey {
+  uint64_t key;
+  uint32_t val;
+  uint32_t pad;
+} WdDetSortKey;
+int64_t wd_det_match_workspace_bytes(int32_t dets_kept, int32_t gts);
+int32_t wd_det_match_lds_bytes(void);
+int wd_det_match(const int32_t* pair_det_off, const int32_t* pair_gt_off, const int32_t* pair_slot_off,
+                 const int32_t* pair_cat, const int64_t* pair_scratch, int32_t n_pair, const float* det_box,
+                 const float* det_score, const uint8_t* det_flag, const double* gt_box, const double* gt_area,
+                 const uint8_t* gt_flag, const double* iou_thr, const double* area_rng, int32_t max_det,
+                 uint8_t* scratch, float* slot_score, int32_t* slot_rank, WdDetSortKey* sort_keys, uint8_t* flags,
+                 int32_t n_slot, int32_t* npig, int32_t* err, void* stream);
+/* Ascending in-place sort of n2 (a power of two >= 2) elements compared as (key, val); padding elements hold all
+ * ones and sort last.  Bitonic network of csrc/bitonic.h (shared with the top-k sort). */
+int wd_det_sort(WdDetSortKey* sort_keys, int64_t n2, void* stream);
+/* accumulate(): permutes slot_rank / slot_score / flags into the sorted order given by the val fields of
+ * sorted_keys (after wd_det_sort), then per (category k, area a, max_dets[m], threshold t) writes precision / scores [10, 101, n_cat,
+ * 4, n_maxdet] and recall [10, n_cat, 4, n_maxdet] (float64; scores may be NULL).  Category k owns the sorted
+ * positions [cat_slot_off[k], cat_slot_off[k+1]) and the pairs [cat_pair_off[k], cat_pair_off[k+1]).  Slices
+ * whose category has no kept gt in the range are not written: the caller fills the outputs with -1. */
+int wd_det_accumulate(const WdDetSortKey* sorted_keys, int32_t n_slot, const int32_t* slot_rank, const float* slot_score,
+                      const uint8_t* flags, int32_t* sorted_rank, float* sorted_score, uint8_t* sorted_flags,
+                      const int32_t* cat_slot_off, const int32_t* cat_pair_off, const int32_t* npig, int32_t n_cat,
+                      const double* rec_thr, const int32_t* max_dets, int32_t n_maxdet, double* precision,
+                      double* recall, double* scores, void* stream);
+
 /* wd_layernorm_rows with the output written as fp16 (hi, lo) groups (see WD_SPLIT_A); c % 8 == 0. */
 int wd_layernorm_rows_split(const float* x, void* y, const float* gamma, const float* beta, int64_t rows, int32_t c,
                             int32_t ldx, int32_t ldy, float eps, void* stream);

@@ -1,0 +1,162 @@
+"""Evaluate a detector checkpoint on the config's test dataset: COCO box mAP (``CocoMetric``) or LVIS mAP
+(``LVISMetric``), with the detector and the metric's matching / accumulation on the device.  Command-line compatible
+with the reference's ``test.py`` (``config checkpoint --work-dir --out --cfg-options --launcher --local-rank``):
+
+    python test.py config/wedetect_base.py ckpt.pth --text-bank bank.pt
+    bash dist_test.sh config/wedetect_base.py ckpt.pth 8 --text-bank bank.pt
+    LVIS: --cfg-options test_evaluator.type=LVISMetric test_evaluator.ann_file=... \
+          test_dataloader.dataset.dataset.type=YOLOv5LVISV1Dataset test_dataloader.dataset.dataset.ann_file=... ...
+          (README.md has the full line; or point test_dataloader / test_evaluator at the LVIS sections of the config)
+
+Flow: contiguous shard of the dataset per rank (``parallel.shard_range``) -> batches of
+``test_dataloader.batch_size`` through the test pipeline and ``YOLOWorldDetector.test_step`` -> per-image predictions
+on the host, gathered to rank 0 -> rank 0 evaluates, prints the metric lines and writes ``<work_dir>/metrics.json``.
+``--out x.pkl`` pickles the per-image result dicts (mmdet ``DumpDetResults``).
+
+Additions: ``--text-bank FILE`` (a precomputed ``[K, 768]`` bank for the K class texts, ``.npy`` / ``.pt``: the XLM-R
+tokenizer files are not needed), ``--precision {fp32,fp16x3}``.  ``--show``, ``--show-dir`` and ``--tta`` are not
+implemented and exit with a message.  A batch size above 1 may change predictions in the last bits (split-K choices
+of small batches).
+"""
+import argparse
+import json
+import os
+import os.path as osp
+import pickle
+import sys
+import time
+
+ROOT = osp.dirname(osp.abspath(__file__))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+
+def parse_args(argv=None):
+    from wedetect_amd.cfgfile import DictAction
+    parser = argparse.ArgumentParser(description="WeDetect test (and eval) a model")
+    parser.add_argument("config", help="test config file path")
+    parser.add_argument("checkpoint", help="checkpoint file")
+    parser.add_argument("--work-dir", help="the directory to save the file containing evaluation metrics")
+    parser.add_argument("--out", type=str, help="dump predictions to a pickle file for offline evaluation")
+    parser.add_argument("--show", action="store_true", help="show prediction results (not implemented)")
+    parser.add_argument("--show-dir", help="directory where painted images will be saved (not implemented)")
+    parser.add_argument("--cfg-options", nargs="+", action=DictAction,
+                        help="override some settings in the used config, the key-value pair in xxx=yyy format will be "
+                             "merged into config file.")
+    parser.add_argument("--launcher", choices=["none", "pytorch", "slurm", "mpi"], default="none", help="job launcher")
+    parser.add_argument("--tta", action="store_true", help="test time augmentation (not implemented)")
+    parser.add_argument("--local_rank", "--local-rank", type=int, default=0)
+    parser.add_argument("--text-bank", default=None, help="precomputed [K, 768] class embeddings (.npy / .pt)")
+    parser.add_argument("--precision", default=None, choices=["fp32", "fp16x3"])
+    args = parser.parse_args(argv)
+    if "LOCAL_RANK" not in os.environ:
+        os.environ["LOCAL_RANK"] = str(args.local_rank)
+    for flag, on in (("--show", args.show), ("--show-dir", args.show_dir), ("--tta", args.tta)):
+        if on:
+            parser.exit(2, f"test.py: {flag} is not implemented on this path (visualisation and flip TTA are out of "
+                           f"scope); run without it\n")
+    if args.launcher in ("slurm", "mpi"):
+        parser.exit(2, f"test.py: --launcher {args.launcher} is not implemented; use --launcher pytorch (dist_test.sh)\n")
+    if args.out is not None and not args.out.endswith((".pkl", ".pickle")):
+        parser.exit(2, "test.py: the output file must be a pkl file.\n")
+    return args
+
+
+def load_bank(path: str):
+    import numpy as np
+    import torch
+    bank = np.load(path) if path.endswith(".npy") else torch.load(path, map_location="cpu")
+    if isinstance(bank, dict):
+        bank = bank.get("text_embedding", next(iter(bank.values())))
+    return torch.as_tensor(np.asarray(bank), dtype=torch.float32)
+
+
+def predict_shard(model, dataset, indices, batch_size: int):
+    """Per-image result dicts (host tensors) of ``indices``, in order."""
+    import torch
+    out = []
+    idx = list(indices)
+    for lo in range(0, len(idx), batch_size):
+        infos = [dataset.get_data_info(i) for i in idx[lo:lo + batch_size]]
+        items = [dataset.pipeline(info) for info in infos]
+        data = dict(inputs=torch.stack([it["inputs"] for it in items]), data_samples=[it["data_samples"] for it in items])
+        with torch.no_grad():
+            outputs = model.test_step(data)
+        for info, o in zip(infos, outputs):
+            p = o.pred_instances
+            out.append(dict(img_id=int(info["img_id"]), img_path=info.get("img_path"),
+                            pred_instances=dict(bboxes=p.bboxes.detach().float().cpu(), scores=p.scores.detach().float().cpu(),
+                                                labels=p.labels.detach().long().cpu())))
+    return out
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    import torch
+    import torch.distributed as dist
+    from wedetect_amd import parallel
+    from wedetect_amd.apis import init_detector
+    from wedetect_amd.cfgfile import Config
+    from wedetect_amd.datasets import build_dataset, build_metric, metric_lines
+
+    cfg = Config.fromfile(args.config)
+    if args.cfg_options is not None:
+        cfg.merge_from_dict(args.cfg_options)
+    if args.work_dir is not None:
+        cfg.work_dir = args.work_dir
+    elif cfg.get("work_dir", None) is None:
+        cfg.work_dir = osp.join("./work_dirs", osp.splitext(osp.basename(args.config))[0])
+
+    if args.launcher == "pytorch":
+        dist.init_process_group("gloo")                 # the gather moves host objects only
+    rank = dist.get_rank() if dist.is_initialized() else 0
+    world = dist.get_world_size() if dist.is_initialized() else 1
+    local = int(os.environ.get("LOCAL_RANK", args.local_rank))
+    device = f"cuda:{local}"
+    torch.cuda.set_device(local)
+
+    dataset = build_dataset(cfg.test_dataloader.dataset)
+    texts = dataset.class_texts
+    if texts is None:
+        texts = [[name] for name in dataset.metainfo["classes"]]
+        dataset.class_texts = texts
+    model = init_detector(cfg, checkpoint=args.checkpoint, device=device, precision=args.precision)
+    if args.text_bank:
+        bank = load_bank(args.text_bank)
+        if tuple(bank.shape) != (len(texts), 768):
+            raise SystemExit(f"--text-bank holds {tuple(bank.shape)}, expected ({len(texts)}, 768): one row per class text")
+        model.set_text_embeddings(bank.to(device), texts)
+    batch_size = int(cfg.test_dataloader.get("batch_size", 1))
+    shard = parallel.shard_range(len(dataset), world, rank)
+    t0 = time.time()
+    preds = predict_shard(model, dataset, shard, batch_size)
+    print(f"[rank {rank}] {len(preds)} images in {time.time() - t0:.1f} s", flush=True)
+    preds = parallel.gather_to_rank0(preds)
+    if rank == 0:
+        if args.out:
+            d = osp.dirname(osp.abspath(args.out))
+            os.makedirs(d, exist_ok=True)
+            with open(args.out, "wb") as f:
+                pickle.dump(preds, f)
+        metric = build_metric(cfg.test_evaluator)
+        metric.process([dict(img_id=p["img_id"], bboxes=p["pred_instances"]["bboxes"].numpy(),
+                             scores=p["pred_instances"]["scores"].numpy(),
+                             labels=p["pred_instances"]["labels"].numpy()) for p in preds])
+        metrics = metric.compute_metrics(device=device)
+        if metrics:
+            for line in metric_lines(metric.eval, metric.lvis):
+                print(line)
+            for name, ap in metric.eval.get("classwise", []):
+                print(f"{name:<24} {ap:.3f}")
+            print(json.dumps(metrics))
+            os.makedirs(cfg.work_dir, exist_ok=True)
+            with open(osp.join(cfg.work_dir, "metrics.json"), "w") as f:
+                json.dump(metrics, f, indent=1)
+    if dist.is_initialized():
+        dist.barrier()
+        dist.destroy_process_group()
+    return metrics if rank == 0 else None
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])

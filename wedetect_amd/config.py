@@ -231,3 +231,4 @@ def _register_text_backbone():
 
 _register_text_backbone()
 from . import detector as _detector  # noqa: E402,F401  (registers YOLOWorldDetector / MultiModalYOLOBackbone)
+from . import datasets as _datasets  # noqa: E402,F401  (registers the test datasets and CocoMetric / LVISMetric)

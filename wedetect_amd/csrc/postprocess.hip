@@ -14,6 +14,7 @@
 // kept boxes, which equals slicing the full NMS result (greedy NMS is prefix-consistent).
 // Three forms (WD_NMS_*): label-test vanilla, torchvision.ops.batched_nms, mmcv.ops.batched_nms —
 // the latter two with the libraries' fp32 coordinate offsets and their candidate-count branches.
+#include "bitonic.h"
 #include "common.h"
 
 #pragma clang fp contract(off)
@@ -252,18 +253,6 @@ __device__ __forceinline__ int sort_n2(unsigned want) {
   return n2;
 }
 
-__device__ __forceinline__ void lds_bitonic_pass(unsigned long long* sk, int chunk, int base, int jj, int dir_bit) {
-  for (int i = threadIdx.x; i < chunk; i += 1024) {
-    const int p = i ^ jj;
-    if (p > i) {
-      const unsigned long long a = sk[i], c = sk[p];
-      const bool up = ((base + i) & dir_bit) == 0;
-      if ((a > c) == up) { sk[i] = c; sk[p] = a; }
-    }
-  }
-  __syncthreads();
-}
-
 // size == 0: phase A (full local sort of the chunk); size > chunk: tail strides of that merge
 __global__ void __launch_bounds__(1024) topk_sort_chunk_kernel(unsigned long long* __restrict__ keys, int cap,
                                                                const TopkState* __restrict__ state, int size) {
@@ -278,9 +267,9 @@ __global__ void __launch_bounds__(1024) topk_sort_chunk_kernel(unsigned long lon
   __syncthreads();
   if (size == 0) {
     for (int sz = 2; sz <= chunk; sz <<= 1)
-      for (int jj = sz >> 1; jj > 0; jj >>= 1) lds_bitonic_pass(sk, chunk, base, jj, sz);
+      for (int jj = sz >> 1; jj > 0; jj >>= 1) wd_lds_bitonic_pass<1024>(sk, chunk, base, jj, sz);
   } else {
-    for (int jj = chunk >> 1; jj > 0; jj >>= 1) lds_bitonic_pass(sk, chunk, base, jj, size);
+    for (int jj = chunk >> 1; jj > 0; jj >>= 1) wd_lds_bitonic_pass<1024>(sk, chunk, base, jj, size);
   }
   for (int i = t; i < chunk; i += 1024) k[i] = sk[i];
 }
@@ -294,12 +283,7 @@ __global__ void __launch_bounds__(256) topk_sort_global_kernel(unsigned long lon
   unsigned long long* k = keys + (size_t)b * cap;
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n2) return;
-  const int p = i ^ j;
-  if (p > i) {
-    const unsigned long long a = k[i], c = k[p];
-    const bool up = (i & size) == 0;
-    if ((a > c) == up) { k[i] = c; k[p] = a; }
-  }
+  wd_global_bitonic_step(k, i, j, size);
 }
 
 __global__ void __launch_bounds__(256) topk_unpack_kernel(const unsigned long long* __restrict__ keys, int cap,

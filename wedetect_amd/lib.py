@@ -33,6 +33,7 @@ EXPORTS = (
     "wd_layernorm_rows", "wd_l2norm_rows", "wd_dfl_decode", "wd_topk_workspace_bytes", "wd_topk_capacity",
     "wd_topk_candidates", "wd_nms_workspace_bytes", "wd_nms_gather", "wd_retrieval_max",
     "wd_split_weights_bytes", "wd_split_weights", "wd_split_weights_padded", "wd_dwconv7_stats", "wd_ln_stats_finalize", "wd_conv_gemm_split", "wd_conv_gemm_split_ws", "wd_conv_gemm_split_config", "wd_layernorm_rows_split", "wd_layernorm_rows_split_s2d", "wd_letterbox_u8", "wd_retrieval_max_split", "wd_similarity_split", "wd_mlp_fused_wide_ln", "wd_text_embed", "wd_attention_small", "wd_recall_scratch_floats", "wd_recall_match",
+    "wd_det_match_workspace_bytes", "wd_det_match_lds_bytes", "wd_det_match", "wd_det_sort", "wd_det_accumulate",
     "wd_max_sigmoid_attn", "wd_adaptive_maxpool_nhwc", "wd_cross_attention_small", "wd_time_next_gemm",
     "wd_cv_resize_paste_u8", "wd_chw_to_hwc_u8", "wd_p8_workspace_bytes", "wd_dwconv7_ln", "wd_probe_lds_dma", "wd_probe_issue", "wd_mlp_fused_split", "wd_mlp_fused_wide", "wd_stem_fused",
 )
@@ -115,6 +116,13 @@ def _load():
     lib.wd_recall_scratch_floats.restype = i64
     lib.wd_recall_scratch_floats.argtypes = [i32, i32]
     lib.wd_recall_match.argtypes = [vp, vp, vp, vp, i32, vp, i32, vp, i64, vp, i32, i32, vp]
+    lib.wd_det_match_workspace_bytes.restype = i64
+    lib.wd_det_match_workspace_bytes.argtypes = [i32, i32]
+    lib.wd_det_match_lds_bytes.restype = i32
+    lib.wd_det_match_lds_bytes.argtypes = []
+    lib.wd_det_match.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp]
+    lib.wd_det_sort.argtypes = [vp, i64, vp]
+    lib.wd_det_accumulate.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp]
     lib.wd_text_embed.argtypes = [vp, vp, vp, vp, vp, vp, i64, i32, vp]
     lib.wd_attention_small.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
     lib.wd_max_sigmoid_attn.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]

@@ -437,3 +437,18 @@ def class_sharded_retrieval(embeddings: torch.Tensor, count: torch.Tensor, scale
     dist.all_gather_into_tensor(blocks, padded, group=group)
     blocks = blocks.view(world, n_total, widest)
     return torch.cat([blocks[r][:, : len(shard_range(n_classes, world, r))] for r in range(world)], dim=1)
+
+
+def gather_to_rank0(items: list, group=None) -> Optional[list]:
+    """Host objects of every rank (a list each, possibly empty) concatenated in rank order on rank 0 (``None`` on the
+    other ranks; the list itself without a process group).  test.py gathers its per-image predictions this way: a few
+    KB per image, so a pickled object gather is enough."""
+    if not (dist.is_available() and dist.is_initialized()):
+        return list(items)
+    world = dist.get_world_size(group)
+    rank = dist.get_rank(group)
+    out = [None] * world if rank == 0 else None
+    dist.gather_object(list(items), out, dst=0, group=group)
+    if rank != 0:
+        return None
+    return [x for part in out for x in part]

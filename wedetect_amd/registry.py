@@ -74,6 +74,8 @@ class Registry:
 
 MODELS = Registry("model")
 TRANSFORMS = Registry("transform")
+DATASETS = Registry("dataset")          # test-mode datasets (wedetect_amd/datasets.py)
+METRICS = Registry("metric")            # box-mAP evaluators (wedetect_amd/datasets.py)
 
 
 def register_with_mmengine() -> bool:
