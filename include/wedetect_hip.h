@@ -293,6 +293,25 @@ int wd_similarity_split(const void* e_split, int64_t rows, const void* t_split, 
                         int32_t dim, int32_t ldo, int32_t seg_rows, int32_t seg_end0, int32_t seg_end1,
                         const float* seg_scale, const float* seg_bias, int32_t sigmoid, uint32_t* range_flag, void* stream);
 
+/* wd_similarity_grouped (ABI 15) — the region x text similarity with ONE TEXT BANK PER IMAGE: the reference takes the class
+ * list per data sample (`texts = [data_sample.texts for data_sample in batch_data_samples]`, wedetect/models/detectors/
+ * yolo_world.py:94-96) and BNContrastiveHead.forward contracts 'bchw,bkc->bkhw' with a [B, K, 768] bank
+ * (dense_heads/yolo_world_head.py:90-108; the sigmoid of predict_by_feat, :664).  One launch for the whole batch:
+ *   out[b][n][c] (row stride ldo, image stride rows_per_img * ldo), b < n_img, n < rows_per_img, c < k_max
+ *     = (sigmoid)( <embed[b][n][:], bank[b][c][:]> * seg_scale[l] + seg_bias[l] )   for c <  count[b]
+ *     = +0.0f (sign bit clear)                                                       for c >= count[b]
+ *   with l = (n >= seg_end0) + (n >= seg_end1), the pyramid level of anchor n — the `seg` epilogue of wd_conv_gemm with
+ *   seg_rows = rows_per_img.  embed [n_img][rows_per_img][dim] and bank [n_img][k_max][dim] are dense fp32, 16-byte aligned,
+ *   dim % 4 == 0; rows of a bank at or above count[b] are never read.  count: DEVICE int32 [n_img], read by the kernel (no
+ *   host read), clamped to [0, k_max]; NULL = k_max for every image.  seg_scale / seg_bias: HOST float[3].  ldo >= k_max;
+ *   columns [k_max, ldo) of a row are not written.  Any k_max / ldo (16-byte stores when ldo % 4 == 0 and out is aligned).
+ * fp32 MFMA, the channels summed in the order of wd_conv_gemm: a valid element is bit-identical to the shared-bank launch
+ * of wd_conv_gemm on image b with the first count[b] rows of bank[b].  Column tiles (80 classes) wholly above count[b] do
+ * no loads and no MFMAs.  There is no fp16x3 form: per-image banks run this kernel at every k_max in both precisions. */
+int wd_similarity_grouped(const float* embed, const float* bank, const int32_t* count, float* out, int32_t n_img,
+                          int32_t rows_per_img, int32_t k_max, int32_t dim, int32_t ldo, int32_t seg_end0, int32_t seg_end1,
+                          const float* seg_scale, const float* seg_bias, int32_t sigmoid, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Text tower pieces (mm_backbone.py:341-390, HF XLMRobertaModel): the embedding
  * sum before the embedding LayerNorm, and self-attention for short sequences.  Everything else of

@@ -186,7 +186,7 @@ class _TowerHolder:
         tower.calibrate(images_u8, merge=True)
         self._share_scales(tower)
 
-    def detect(self, tower, images_u8, text, meta, **kw):
+    def detect(self, tower, images_u8, text, meta, text_counts=None, **kw):
         """``tower.detect`` for the detector classes.  Small batches (the reference runs batch 1 everywhere) are
         launch-bound, so the step is replayed from a hipGraph captured on first use (engine.GraphedDetect: inputs are
         copied into the graph's static buffers, results are the tower's usual buffers — bit-identical to the eager
@@ -200,6 +200,10 @@ class _TowerHolder:
                 self._share_scales(tower)
             else:
                 tower.adopt_scales(self.sscale)
+        if text.dim() == 3 or text_counts is not None:
+            # one bank per image ([B, k_max, 768] + device counts): always the eager step, never captured — a graph would
+            # have to own a static copy of every packed bank, and a batch of per-image banks is not launch-bound
+            return tower.detect(images_u8, text, meta, text_counts=text_counts, **kw)
         if tower.B > self.graph_max_batch:
             return tower.detect(images_u8, text, meta, **kw)
         k = int(text.shape[0])
@@ -527,6 +531,45 @@ def _flat_texts(texts) -> Tuple[str, ...]:
     return tuple((t[0] if isinstance(t, (list, tuple)) else t) for t in texts)
 
 
+# Per-image banks are packed to [b, k_max, 768] with k_max rounded UP to a multiple of this.  The tower sizes its score,
+# top-k and normalised-bank buffers by the largest k_max it has seen and re-allocates (dropping captured graphs) whenever
+# a larger one arrives: with the rounding a stream of batches whose longest class list wanders (37, 41, 44 ...) settles after
+# a few sizes instead of re-allocating at every new maximum.  16 keeps the padding the top-k has to read below 16 columns
+# (none at the usual 80), and a multiple of 4 keeps every score row 16-byte aligned for the kernel's vector stores.
+BANK_K_ROUND = 16
+
+
+def round_bank_k(k: int) -> int:
+    """k_max of a packed bank for a longest class list of ``k`` rows."""
+    if k < 1:
+        raise ValueError("a class bank needs at least one row")
+    return -(-int(k) // BANK_K_ROUND) * BANK_K_ROUND
+
+
+def bank_pack_key(banks: Sequence[torch.Tensor]) -> Optional[Tuple[int, ...]]:
+    """Cache key of a batch's banks: None when every sample carries the SAME bank object (the shared-bank step), else the
+    identities of the bank objects in sample order (a cache entry keeps the objects alive, so an id cannot be recycled
+    while its entry exists)."""
+    if not banks:
+        raise ValueError("no banks")
+    if all(b is banks[0] for b in banks):
+        return None
+    return tuple(id(b) for b in banks)
+
+
+def pack_image_banks(banks: Sequence[torch.Tensor], device=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Banks [k_i, 768] of one batch -> (packed [b, k_max, 768] float32 with zero rows below each bank, counts int32 [b]),
+    both on ``device``; k_max = round_bank_k(max k_i).  Rows are copied as they are (the tower normalises on the device)."""
+    for b in banks:
+        if b.dim() != 2 or b.shape[1] != EMBED_DIM or b.shape[0] < 1:
+            raise ValueError(f"a class bank must be [K >= 1, {EMBED_DIM}], got {tuple(b.shape)}")
+    ks = [int(b.shape[0]) for b in banks]
+    packed = torch.zeros(len(banks), round_bank_k(max(ks)), EMBED_DIM, dtype=torch.float32, device=device)
+    for i, b in enumerate(banks):
+        packed[i, : ks[i]].copy_(b)
+    return packed, torch.tensor(ks, dtype=torch.int32).to(packed.device)
+
+
 class MultiModalYOLOBackbone:
     """``model.backbone`` of the reference detector (mm_backbone.py:594-656) as far as inference callers touch it:
     ``forward_text(texts)`` and ``with_text_model``.  The image side is the fused ``ImageTower``; it has no
@@ -626,6 +669,8 @@ class YOLOWorldDetector(_DeviceModule):
         self.texts = None
         self.text_feats: Optional[torch.Tensor] = None
         self._banks: Dict[Tuple[str, ...], torch.Tensor] = {}
+        # packed per-image banks of recurring bank combinations: key -> (the bank objects, packed [b, k_max, 768], counts)
+        self._packed_banks: "OrderedDict[Tuple[int, ...], tuple]" = OrderedDict()
 
     # -- weights --------------------------------------------------------------------------
     def _load_state(self, state_dict, strict: bool):
@@ -638,6 +683,7 @@ class YOLOWorldDetector(_DeviceModule):
             elif strict:
                 raise RuntimeError("Error(s) in loading state_dict: no backbone.text_model.* tensors in the checkpoint")
         self._banks.clear()
+        self._packed_banks.clear()
         self.text_feats = self.texts = None
         return msg
 
@@ -699,6 +745,24 @@ class YOLOWorldDetector(_DeviceModule):
             bank = self._banks[flat] = self._encode(flat).detach().to(torch.float32)
         return bank
 
+    PACKED_BANKS_MAX = 16          # cached combinations (32 banks of 80 rows: 7.9 MB each)
+
+    def _packed_for(self, banks: List[torch.Tensor], dev):
+        """None when the whole batch shares one bank object; else the packed banks and device counts of this combination,
+        built once (pack_image_banks) and kept while the combination recurs."""
+        key = bank_pack_key(banks)
+        if key is None:
+            return None
+        hit = self._packed_banks.get(key)
+        if hit is not None and hit[1].device == dev and all(a is b for a, b in zip(hit[0], banks)):
+            self._packed_banks.move_to_end(key)
+            return hit[1], hit[2]
+        while len(self._packed_banks) >= self.PACKED_BANKS_MAX:
+            self._packed_banks.popitem(last=False)
+        packed, counts = pack_image_banks(banks, dev)
+        self._packed_banks[key] = (tuple(banks), packed, counts)
+        return packed, counts
+
     # -- image side -----------------------------------------------------------------------
     @torch.no_grad()
     def test_step(self, data: dict):
@@ -733,48 +797,52 @@ class YOLOWorldDetector(_DeviceModule):
         if hh % 32 or ww % 32:
             raise ValueError(f"input size {hh}x{ww} is not a multiple of 32 (letterbox to img_scale first)")
         out: List[Optional[DetDataSample]] = [None] * len(xs)
-        groups: Dict[int, List[int]] = {}
-        for i, bk in enumerate(banks):
-            groups.setdefault(id(bk), []).append(i)
-        for idxs in groups.values():
-            from . import lib as L
-            chw = torch.stack([xs[i].to(dev) for i in idxs])     # [b, 3, H, W] BGR, contiguous
-            if chw.dtype not in (torch.uint8, torch.float32):
-                chw = chw.to(torch.float32)
-            x = torch.empty(len(idxs), hh, ww, 3, dtype=torch.uint8, device=dev)
-            L.chw_to_hwc_u8(chw, x)                              # bgr_to_rgb + NHWC (data_preprocessor.py:35-36)
-            metas = []
-            for i in idxs:
-                m = _meta_of(samples[i])
-                ori = m.get("ori_shape", (hh, ww))
-                sf = m.get("scale_factor", (1.0, 1.0))
-                pad = m.get("pad_param", None)
-                px, py = (0.0, 0.0) if pad is None else (float(pad[2]), float(pad[0]))
-                sx, sy = (float(sf[0]), float(sf[1])) if rescale else (1.0, 1.0)
-                if not rescale:
-                    px = py = 0.0
-                metas.append([px, py, 0.0, sx, sy, float(ori[1]), float(ori[0]), 1.0])
-            tower = self._h.tower(len(idxs), hh, ww)
-            meta = torch.tensor(metas, dtype=torch.float32, device=dev)
-            bank = banks[idxs[0]].to(dev)
-            run = lambda: self._h.detect(tower, x, bank, meta, normalize_text=True, score_thr=self.test_cfg["score_thr"],
-                                         iou_thr=self.test_cfg["nms"]["iou_threshold"], with_embed=False,
-                                         # mmdet _bbox_post_process -> mmcv.ops.batched_nms(bboxes, scores, labels, cfg.nms)
-                                         nms="mmcv", nms_param=int(self.test_cfg["nms"].get("split_thr", 10000)))
-            res = run()
-            recal = (lambda: self._h.recalibrate(tower, x)) if self._h.auto_calibrate else None
-            counts = tower.checked_counts(res, run, recal)
-            self._h.precision = "fp32" if tower.overflowed else self._h._asked_precision
-            for j, (i, n) in enumerate(zip(idxs, counts)):
-                inst = InstanceData(bboxes=res["bboxes"][j, :n].clone(), scores=res["scores"][j, :n].clone(),
-                                    labels=res["labels"][j, :n].to(torch.int64))
-                s = samples[i]
-                if s is None:
-                    s = DetDataSample()
-                elif isinstance(s, dict):
-                    s = DetDataSample(metainfo=_meta_of(s))
-                s.pred_instances = inst
-                out[i] = s
+        # ONE tower step for the batch, whatever the samples' class lists: one bank object for all -> the shared-bank step;
+        # otherwise the banks travel as [b, k_max, 768] + device counts and every image is scored against its own
+        # (yolo_world.py:94-96: ``texts = [data_sample.texts for data_sample in batch_data_samples]``)
+        from . import lib as L
+        idxs = list(range(len(xs)))
+        packed = self._packed_for(banks, dev)
+        chw = torch.stack([xs[i].to(dev) for i in idxs])     # [b, 3, H, W] BGR, contiguous
+        if chw.dtype not in (torch.uint8, torch.float32):
+            chw = chw.to(torch.float32)
+        x = torch.empty(len(idxs), hh, ww, 3, dtype=torch.uint8, device=dev)
+        L.chw_to_hwc_u8(chw, x)                              # bgr_to_rgb + NHWC (data_preprocessor.py:35-36)
+        metas = []
+        for i in idxs:
+            m = _meta_of(samples[i])
+            ori = m.get("ori_shape", (hh, ww))
+            sf = m.get("scale_factor", (1.0, 1.0))
+            pad = m.get("pad_param", None)
+            px, py = (0.0, 0.0) if pad is None else (float(pad[2]), float(pad[0]))
+            sx, sy = (float(sf[0]), float(sf[1])) if rescale else (1.0, 1.0)
+            if not rescale:
+                px = py = 0.0
+            metas.append([px, py, 0.0, sx, sy, float(ori[1]), float(ori[0]), 1.0])
+        tower = self._h.tower(len(idxs), hh, ww)
+        meta = torch.tensor(metas, dtype=torch.float32, device=dev)
+        if packed is None:
+            bank, counts_dev = banks[0].to(dev), None
+        else:
+            bank, counts_dev = packed
+        run = lambda: self._h.detect(tower, x, bank, meta, text_counts=counts_dev, normalize_text=True, score_thr=self.test_cfg["score_thr"],
+                                     iou_thr=self.test_cfg["nms"]["iou_threshold"], with_embed=False,
+                                     # mmdet _bbox_post_process -> mmcv.ops.batched_nms(bboxes, scores, labels, cfg.nms)
+                                     nms="mmcv", nms_param=int(self.test_cfg["nms"].get("split_thr", 10000)))
+        res = run()
+        recal = (lambda: self._h.recalibrate(tower, x)) if self._h.auto_calibrate else None
+        counts = tower.checked_counts(res, run, recal)
+        self._h.precision = "fp32" if tower.overflowed else self._h._asked_precision
+        for j, (i, n) in enumerate(zip(idxs, counts)):
+            inst = InstanceData(bboxes=res["bboxes"][j, :n].clone(), scores=res["scores"][j, :n].clone(),
+                                labels=res["labels"][j, :n].to(torch.int64))
+            s = samples[i]
+            if s is None:
+                s = DetDataSample()
+            elif isinstance(s, dict):
+                s = DetDataSample(metainfo=_meta_of(s))
+            s.pred_instances = inst
+            out[i] = s
         return out
 
 

@@ -339,6 +339,7 @@ class ImageTower:
         self.out_count = torch.empty(B, dtype=torch.int32, device=self.dev)
         self.out_embed = f(B, max_out, EMBED_DIM)
         self.text_norm = f(max_classes, EMBED_DIM)
+        self.text_norm_pi: Optional[torch.Tensor] = None      # normalised per-image banks [B * k_max, 768], allocated on first use
         # per-level exp(logit_scale) in fp32 like ``logit_scale.exp()`` on a float32 parameter
         self.lvl_scale = [float(np.exp(np.float32(self.P.s[f"head{l}.logit_scale"]))) for l in range(3)]
         self.lvl_bias = [float(np.float32(self.P.s[f"head{l}.bias"])) for l in range(3)]
@@ -1128,10 +1129,21 @@ class ImageTower:
         return self.embed, self.boxes
 
     # ------------------------------------------------------------------ similarity
-    def similarity(self, text: torch.Tensor, normalize: bool, sigmoid: bool = True) -> torch.Tensor:
+    def similarity(self, text: torch.Tensor, normalize: bool, sigmoid: bool = True,
+                   text_counts: Optional[torch.Tensor] = None) -> torch.Tensor:
         """scores[b, n, k] = sigmoid(<embed[b,n], t_k> * exp(logit_scale_lvl) + bias_lvl).
         ``normalize``: L2-normalise the text rows first (BNContrastiveHead, yolo_world_head.py:101);
-        the Uni path uses its prompt rows as stored (generate_proposal.py:1130)."""
+        the Uni path uses its prompt rows as stored (generate_proposal.py:1130).
+
+        ``text`` [K, 768]: one bank for the whole batch.  ``text`` [B, k_max, 768]: ONE BANK PER IMAGE (the reference's
+        per-sample ``texts``, yolo_world.py:94-96, and its 'bchw,bkc->bkhw', yolo_world_head.py:90-108), image b scored against
+        its first ``text_counts[b]`` rows — ``text_counts`` a DEVICE int32 [B] tensor (read by the kernel: no host read in
+        the step), None = all k_max rows.  Returns [B, N, k_max] with ``scores[b, :, text_counts[b]:] == +0``; a valid
+        element has the bits the shared-bank call gives for image b with that image's own bank (wd_similarity_grouped).
+        Per-image banks run the fp32 MFMA kernel at every k_max in BOTH tower precisions: there is no fp16x3 form of it
+        (the embeddings and the bank are fp32 in both modes)."""
+        if text.dim() == 3 or text_counts is not None:
+            return self._similarity_per_image(text, normalize, sigmoid, text_counts)
         k = text.shape[0]
         if text.dtype != torch.float32 or text.shape[1] != EMBED_DIM or not text.is_cuda:
             raise L.WedetectHipError("text bank must be a device float32 [K, 768] tensor")
@@ -1154,6 +1166,36 @@ class ImageTower:
             t = self.text_norm[:k]
         L.conv_gemm(self.embed, t, None, out, batch=1, hin=1, win=self.B * self.ntot, cin=EMBED_DIM, lda=EMBED_DIM,
                     n=k, ldc=k, sigmoid=sigmoid, seg=seg)
+        return out
+
+    def _similarity_per_image(self, text: torch.Tensor, normalize: bool, sigmoid: bool,
+                              text_counts: Optional[torch.Tensor]) -> torch.Tensor:
+        if not isinstance(text, torch.Tensor) or text.dim() != 3 or text.dtype != torch.float32 or text.shape[2] != EMBED_DIM \
+                or not text.is_cuda or text.device != self.embed.device or text.shape[1] < 1:
+            raise L.WedetectHipError("per-image text banks must be one device float32 [B, k_max, 768] tensor on the tower's device")
+        if text.shape[0] != self.B:
+            raise L.WedetectHipError(f"per-image text banks: {text.shape[0]} banks for a tower of batch {self.B}")
+        if text_counts is not None:
+            if not isinstance(text_counts, torch.Tensor) or not text_counts.is_cuda or text_counts.device != self.embed.device:
+                raise L.WedetectHipError("text_counts must be a DEVICE int32 [B] tensor (the kernel reads it; the step has no host read)")
+            if text_counts.dtype != torch.int32 or tuple(text_counts.shape) != (self.B,):
+                raise L.WedetectHipError(f"text_counts must be int32 of shape [{self.B}], got {text_counts.dtype} {tuple(text_counts.shape)}")
+            text_counts = text_counts.contiguous()
+        k = text.shape[1]
+        if k > self.max_classes:
+            self._alloc_post(k)
+        t = text.contiguous()
+        if normalize:
+            # every row on its own, as in the shared path: row (b, c) gets the bits the 2-D call gives that row
+            if self.text_norm_pi is None or self.B * k > self.text_norm_pi.shape[0]:
+                self.text_norm_pi = torch.empty(self.B * k, EMBED_DIM, dtype=torch.float32, device=self.dev)
+                self.generation += 1
+            tn = self.text_norm_pi[: self.B * k]
+            L.l2norm_rows(t.view(self.B * k, EMBED_DIM), tn)
+            t = tn.view(self.B, k, EMBED_DIM)
+        out = self.scores.view(-1)[: self.B * self.ntot * k].view(self.B, self.ntot, k)
+        seg = (self.ntot, self.off[1], self.off[2], self.lvl_scale, self.lvl_bias)
+        L.similarity_grouped(self.embed, t, text_counts, out, self.B, self.ntot, k, EMBED_DIM, k, seg, sigmoid=sigmoid)
         return out
 
     def _split_text(self, t: torch.Tensor, normalize: bool):
@@ -1189,7 +1231,13 @@ class ImageTower:
         the box-coordinate count above which it runs per class, 4000 for CPU tensors), "mmcv" (mmdet's
         _bbox_post_process, yolo_world_head.py:740-744; ``nms_param`` = split_thr, 10000) or "vanilla" (label test).
         ``nms_device``: the device kind the reference's tensors would be on — decides torchvision's branch limit default
-        (4000 / 20000 box coordinates) and whether its kernel compares the IoU with a double ("cpu") or a float ("cuda")."""
+        (4000 / 20000 box coordinates) and whether its kernel compares the IoU with a double ("cpu") or a float ("cuda").
+
+        Per-image banks (``similarity(text [B, k_max, 768], text_counts)``) need nothing new here: ``k`` is k_max, a candidate's
+        flat index is ``anchor * k_max + class``, which orders the candidates of image b exactly like ``anchor * count[b] +
+        class`` would — both are lexicographic in (anchor, class) — and a padded column holds +0, which never passes
+        ``score > score_thr`` (score_thr >= 0).  Image b's rows are therefore those of a shared-bank step with its own bank,
+        and its labels are < count[b]."""
         B, n, k = scores.shape
         mode = self.NMS_MODES[nms]
         if nms_param is None:
@@ -1301,8 +1349,9 @@ class ImageTower:
 
     def detect(self, images_u8, text, meta, *, normalize_text: bool, score_thr: float, iou_thr: float = 0.7,
                with_embed: bool = False, nms: Optional[str] = None, nms_param: Optional[int] = None, nms_device: str = "cpu",
-               overlap_post: bool = False):
-        """The whole step.  ``nms`` None picks the library the reference's path of this text handling uses: normalised
+               overlap_post: bool = False, text_counts: Optional[torch.Tensor] = None):
+        """The whole step.  ``text`` [K, 768] (one bank) or [B, k_max, 768] with ``text_counts`` (one bank per image, see
+        similarity(); in line and under ``overlap_post`` alike, same bits).  ``nms`` None picks the library the reference's path of this text handling uses: normalised
         text = BNContrastiveHead of the mmdet path -> "mmcv"; prompts as stored = the Uni scripts -> "torchvision".
 
         ``overlap_post`` (a stream of batches; round 4): the post-process of this step — top-k over B x N x K scores and the
@@ -1318,10 +1367,12 @@ class ImageTower:
         honoured; a later in-line call, ``backbone()`` or ``features()`` orders itself behind the pending work by itself."""
         if nms is None:
             nms = "mmcv" if normalize_text else "torchvision"
+        # the bank size the head prepares the fp16x3 similarity operands for; per-image banks run the fp32 kernel: none
+        num_classes = None if (text.dim() == 3 or text_counts is not None) else text.shape[0]
         if not overlap_post:
             self.wait_post()                      # a pipelined step may still be reading the buffers this one is about to write
-            self.features(images_u8, num_classes=text.shape[0])
-            scores = self.similarity(text, normalize=normalize_text)
+            self.features(images_u8, num_classes=num_classes)
+            scores = self.similarity(text, normalize=normalize_text, text_counts=text_counts)
             return self.postprocess(scores, score_thr, meta, iou_thr, with_embed, nms, nms_param, nms_device)
         if self.post_stream is None:
             self.post_stream = device_streams(self.dev, "post")[0]
@@ -1357,12 +1408,12 @@ class ImageTower:
             try:
                 if self._dag_on():
                     self.wait_post()                  # head level 0 starts inside the neck: the previous post-process must be done with
-                    self.neck_head(text.shape[0])     # boxes / embeddings before ANY head kernel is issued (it had the whole backbone)
+                    self.neck_head(num_classes)       # boxes / embeddings before ANY head kernel is issued (it had the whole backbone)
                 else:
                     self.neck()
                     self.wait_post()
-                    self.head(text.shape[0])
-                scores = self.similarity(text, normalize=normalize_text)
+                    self.head(num_classes)
+                scores = self.similarity(text, normalize=normalize_text, text_counts=text_counts)
             finally:
                 self._nh_issue = False
             self._post_ready.record(nh)
@@ -1372,7 +1423,7 @@ class ImageTower:
                 self._x_free[self._x_par].record(nh)
         # the caller's tensors are read by kernels on post_stream (and the nh stream) after this call returns: tell the caching
         # allocator, or a caller that drops `meta` / `text` right away could see the block reused while they still read it
-        for t_ in (meta, text):
+        for t_ in (meta, text, text_counts):
             if isinstance(t_, torch.Tensor) and t_.is_cuda:
                 t_.record_stream(self.post_stream)
                 if pipe:

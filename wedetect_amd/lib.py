@@ -20,7 +20,7 @@ LIB_PATH = os.environ.get("WEDETECT_LIB") or os.path.join(_HERE, "libwedetect_hi
 ACT_NONE, ACT_RELU, ACT_SILU, ACT_GELU = 0, 1, 2, 3
 OUT_ROWS, OUT_DECONV2X2 = 0, 1
 SPLIT_A, SPLIT_C = 1, 2
-ABI_VERSION = 14
+ABI_VERSION = 15
 NMS_VANILLA, NMS_TORCHVISION, NMS_MMCV = 0, 1, 2
 # torchvision/ops/boxes.py batched_nms: the per-class loop (_batched_nms_vanilla) above this many box coordinates
 # (boxes.numel()).  4000 / 20000 are the values of torchvision 0.15 ... 0.21 (the releases contemporary with the
@@ -32,7 +32,7 @@ EXPORTS = (
     "wd_abi_version", "wd_strerror", "wd_sizeof_conv_gemm", "wd_conv_gemm", "wd_conv_gemm_tuned", "wd_conv_gemm_config", "wd_stem_patchify", "wd_dwconv7", "wd_dwconv7_variant",
     "wd_layernorm_rows", "wd_l2norm_rows", "wd_dfl_decode", "wd_topk_workspace_bytes", "wd_topk_capacity",
     "wd_topk_candidates", "wd_nms_workspace_bytes", "wd_nms_gather", "wd_retrieval_max",
-    "wd_split_weights_bytes", "wd_split_weights", "wd_split_weights_padded", "wd_dwconv7_stats", "wd_ln_stats_finalize", "wd_conv_gemm_split", "wd_conv_gemm_split_ws", "wd_conv_gemm_split_config", "wd_layernorm_rows_split", "wd_layernorm_rows_split_s2d", "wd_letterbox_u8", "wd_retrieval_max_split", "wd_similarity_split", "wd_mlp_fused_wide_ln", "wd_text_embed", "wd_attention_small", "wd_recall_scratch_floats", "wd_recall_match",
+    "wd_split_weights_bytes", "wd_split_weights", "wd_split_weights_padded", "wd_dwconv7_stats", "wd_ln_stats_finalize", "wd_conv_gemm_split", "wd_conv_gemm_split_ws", "wd_conv_gemm_split_config", "wd_layernorm_rows_split", "wd_layernorm_rows_split_s2d", "wd_letterbox_u8", "wd_retrieval_max_split", "wd_similarity_split", "wd_similarity_grouped", "wd_mlp_fused_wide_ln", "wd_text_embed", "wd_attention_small", "wd_recall_scratch_floats", "wd_recall_match",
     "wd_det_match_workspace_bytes", "wd_det_match_lds_bytes", "wd_det_match", "wd_det_sort", "wd_det_accumulate",
     "wd_max_sigmoid_attn", "wd_adaptive_maxpool_nhwc", "wd_cross_attention_small", "wd_time_next_gemm",
     "wd_cv_resize_paste_u8", "wd_chw_to_hwc_u8", "wd_p8_workspace_bytes", "wd_dwconv7_ln", "wd_probe_lds_dma", "wd_probe_issue", "wd_mlp_fused_split", "wd_mlp_fused_wide", "wd_stem_fused",
@@ -107,6 +107,7 @@ def _load():
     lib.wd_split_weights_padded.argtypes = [vp, i32, i32, f32, vp, vp]
     lib.wd_dwconv7_stats.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp]
     lib.wd_similarity_split.argtypes = [vp, i64, vp, f32, vp, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_float), C.POINTER(C.c_float), i32, vp, vp]
+    lib.wd_similarity_grouped.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_float), C.POINTER(C.c_float), i32, vp]
     lib.wd_ln_stats_finalize.argtypes = [vp, vp, i64, i32, f32, vp]
     lib.wd_conv_gemm_split.argtypes = [C.POINTER(ConvGemm), vp, f32, i32, i32, vp]
     lib.wd_conv_gemm_split_ws.argtypes = [C.POINTER(ConvGemm), vp, f32, i32, i32, vp, i64, i32, vp]
@@ -456,6 +457,23 @@ def similarity_split(e_split, rows, t_split, unscale, out, n_cls, dim, ldo, seg=
     sb = (C.c_float * 3)(*[float(v) for v in (seg[4] if seg is not None else (0, 0, 0))])
     check(LIB.wd_similarity_split(_p(e_split), int(rows), _p(t_split), float(unscale), _p(out), int(n_cls), int(dim), int(ldo),
                                   sr, e0, e1, sc, sb, int(bool(sigmoid)), _p(range_flag), stream_ptr()), "wd_similarity_split")
+
+
+def similarity_grouped(embed, bank, count, out, n_img, rows_per_img, k_max, dim, ldo, seg, sigmoid=True) -> None:
+    """Region x text similarity with one bank per image (wd_similarity_grouped): ``embed`` [n_img, rows_per_img, dim],
+    ``bank`` [n_img, k_max, dim], ``count`` a DEVICE int32 [n_img] tensor (None: k_max everywhere), ``out`` rows of stride
+    ``ldo``; columns >= count[b] of image b are +0.  ``seg`` = (rows_per_img, seg_end0, seg_end1, scales, biases) as in
+    :func:`conv_gemm`.  fp32 MFMA at every k_max."""
+    _f32(embed, "embed"), _f32(bank, "bank"), _f32(out, "out")
+    if count is not None and (count.dtype != torch.int32 or not count.is_cuda or count.numel() < n_img or not count.is_contiguous()):
+        raise WedetectHipError(f"count: expected a contiguous CUDA/HIP int32 [{n_img}] tensor, got {count.dtype} on {count.device}")
+    if int(seg[0]) != int(rows_per_img):
+        raise WedetectHipError("seg rows must equal rows_per_img")
+    sc = (C.c_float * 3)(*[float(v) for v in seg[3]])
+    sb = (C.c_float * 3)(*[float(v) for v in seg[4]])
+    check(LIB.wd_similarity_grouped(_p(embed), _p(bank), _p(count), _p(out), int(n_img), int(rows_per_img), int(k_max), int(dim),
+                                    int(ldo), int(seg[1]), int(seg[2]), sc, sb, int(bool(sigmoid)), stream_ptr()),
+          "wd_similarity_grouped")
 
 
 def text_embed(ids, pos_ids, word, pos, type0, out) -> None:
