@@ -158,7 +158,17 @@ int wd_conv_gemm_split(const WdConvGemm* p, const void* w_split, float w_unscale
  *               WD_SPLIT_A: any output addressing (rows, channel slices, c_batch_stride, the 2x2 deconv scatter), an
  *               fp32 residual and an fp32 copy in p->c2 are allowed.  Without WD_SPLIT_A (fp32 activations split by
  *               the loader): plain rows, no residual.
- * Results are bit-identical to the flags = 0 path (the same halves, produced earlier; same K order). */
+ * Results are bit-identical to the flags = 0 path (the same halves, produced earlier; same K order).
+ * Alignment: a WD_SPLIT_C output p->c and its p->bias are 16-byte aligned; with WD_SPLIT_A outside the plain-row 1x1 case
+ * (the LDS-DMA kernels) p->res and p->c2 are 16-byte aligned too, ldres % 4 == 0, ldc2 % 4 == 0.
+ * Extents: p->a holds exactly the batch * hin * win pixel rows of lda floats (nothing is expected behind the last row or in
+ * the columns [cin, lda) of a row: ragged tiles and the convolution halo read a zero page, never the neighbourhood);
+ * w_split needs only the n rows wd_split_weights writes; stores stay inside the n columns of the m output rows.
+ * range_flag reflects rows < m and columns < n only.  This is a property of the LOADERS, not of every epilogue: two epilogues
+ * of split_gemm_impl.h (epi_direct_tile_csplit, EpiResWalk::run) test a tile's accumulators before their m < p.m check, and
+ * stay quiet on ragged tiles only because every loader feeds rows >= m and weight rows >= n from a zero page (or clamps them to
+ * valid rows).  A loader that fetched the neighbourhood instead would trip the flag on finite data next to a NaN / -1 filler;
+ * tests/test_gpu_extents.py runs every family with 0xFF bytes behind a and w_split to hold that line. */
 #define WD_SPLIT_A 1
 #define WD_SPLIT_C 2
 /* wd_conv_gemm_split with a caller-owned workspace (16-byte aligned): when a launch has few tiles and a long
@@ -522,6 +532,8 @@ int wd_dfl_decode(const float* dist, int32_t ld, float* boxes, int32_t batch, in
  * Replaces filter_scores_and_topk (generate_proposal.py:85-131; mmdet twin called at
  * yolo_world_head.py:721-722) with the stabilised total order of SURVEY.md §7.
  * Workspace: wd_topk_workspace_bytes(batch, n, nms_pre) bytes, 256-byte aligned.
+ * Extents: all cap entries of every out_idx / out_score row are written (-1 / 0.f from out_count on); the workspace
+ * needs no initialisation (the call clears what it accumulates into) and nothing is written beyond its stated size.
  * ---------------------------------------------------------------------------------- */
 int64_t wd_topk_workspace_bytes(int32_t batch, int64_t n_per_image, int32_t nms_pre);
 int32_t wd_topk_capacity(int32_t nms_pre);   /* power of two >= nms_pre */
@@ -566,7 +578,9 @@ int wd_topk_candidates(const float* scores, int32_t batch, int64_t n_per_image, 
  *   (int32), out_anchors (int32), out_count [batch]; if embed != NULL also
  *   out_embed [batch, max_out, embed_dim] = embed[b, anchor, :].
  *   Workspace: wd_nms_workspace_bytes(batch) bytes, 4-byte aligned (per-image coordinate
- *   bounds of the offset forms; may be NULL for WD_NMS_VANILLA).
+ *   bounds of the offset forms; may be NULL for WD_NMS_VANILLA); needs no initialisation.
+ *   Extents: all max_out rows of every output are written — from out_count on out_boxes / out_scores /
+ *   out_embed rows are 0 and out_labels / out_anchors are -1.  boxes, out_boxes, embed, out_embed: 16-byte aligned.
  * Replaces torchvision.ops.batched_nms(...)[:300] (generate_proposal.py:1210),
  * mmdet _bbox_post_process -> mmcv.ops.batched_nms + max_per_img
  * (yolo_world_head.py:740-744), and the index gathers at generate_proposal.py:1208-1217.
