@@ -38,6 +38,10 @@ DATASETS = {                                                          # eval_rec
 }
 
 
+def image_file_name(ann: dict) -> str:
+    return ann["file_name"] if "file_name" in ann else ann["coco_url"].replace("http://images.cocodataset.org/", "")
+
+
 class ImageDataset(torch.utils.data.Dataset):
     """eval_recall.py:1421-1466: ``{'id', 'image'}`` per annotation-file image (``coco_url`` for LVIS-style files)."""
 
@@ -50,8 +54,7 @@ class ImageDataset(torch.utils.data.Dataset):
     def __getitem__(self, i):
         from PIL import Image
         ann = self.images[self.indices[i]]
-        name = ann["file_name"] if "file_name" in ann else ann["coco_url"].replace("http://images.cocodataset.org/", "")
-        return {"id": int(ann["id"]), "image": Image.open(os.path.join(self.image_path, name)).convert("RGB")}
+        return {"id": int(ann["id"]), "image": Image.open(os.path.join(self.image_path, image_file_name(ann))).convert("RGB")}
 
 
 def ground_truth_boxes(annotations, image_ids, drop_crowd: bool):
@@ -108,21 +111,29 @@ def run(args):
         ann_file = json.load(f)
     random.seed(args.seed)
     mine = shard_range(len(ann_file["images"]), world, rank)                     # InferenceSampler, 1470-1488
-    loader = torch.utils.data.DataLoader(ImageDataset(ann_file["images"], image_path, mine), batch_size=args.batch_size,
-                                         num_workers=args.num_workers, pin_memory=False, drop_last=False,
-                                         collate_fn=lambda inputs: inputs, shuffle=False)
-    try:
-        from tqdm import tqdm
-        it = tqdm(loader, disable=rank != 0)
-    except ImportError:
-        it = loader
     image_ids, all_boxes = [], []
-    with torch.no_grad():
-        for inputs in it:
-            outputs = model([x["image"] for x in inputs])
-            for x, o in zip(inputs, outputs):
-                image_ids.append(x["id"])
-                all_boxes.append(o["bboxes"].cpu())
+    if args.loader == "stream":
+        # the streamed loader decodes the files itself (threads, pinned arenas): ids and paths only
+        anns = [ann_file["images"][i] for i in mine]
+        paths = [os.path.join(image_path, image_file_name(a)) for a in anns]
+        for a, o in zip(anns, model.predict_stream(paths, args.batch_size, with_embeddings=False, decode_workers=args.decode_workers)):
+            image_ids.append(int(a["id"]))
+            all_boxes.append(o["bboxes"])
+    else:
+        loader = torch.utils.data.DataLoader(ImageDataset(ann_file["images"], image_path, mine), batch_size=args.batch_size,
+                                             num_workers=args.num_workers, pin_memory=False, drop_last=False,
+                                             collate_fn=lambda inputs: inputs, shuffle=False)
+        try:
+            from tqdm import tqdm
+            it = tqdm(loader, disable=rank != 0)
+        except ImportError:
+            it = loader
+        with torch.no_grad():
+            for inputs in it:
+                outputs = model([x["image"] for x in inputs])
+                for x, o in zip(inputs, outputs):
+                    image_ids.append(x["id"])
+                    all_boxes.append(o["bboxes"].cpu())
     dist.barrier()
     merged_ids, merged_boxes = [None] * world, [None] * world
     dist.all_gather_object(merged_ids, image_ids)                                # eval_recall.py:1567-1571
@@ -140,7 +151,7 @@ def run(args):
     return result
 
 
-def main(argv=None):
+def parse_args(argv=None):
     parser = argparse.ArgumentParser()
     parser.add_argument("--wedetect_uni_checkpoint", type=str, default="")
     parser.add_argument("--dataset", type=str, default="")
@@ -151,7 +162,14 @@ def main(argv=None):
     parser.add_argument("--image-path", type=str, default=None)
     parser.add_argument("--precision", default=None, choices=["fp32", "fp16x3"])
     parser.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL)")
-    return run(parser.parse_args(argv))
+    parser.add_argument("--loader", default="serial", choices=["serial", "stream"],
+                        help="serial: the DataLoader loop (default); stream: SimpleYOLOWorldDetector.predict_stream")
+    parser.add_argument("--decode-workers", type=int, default=None, help="--loader stream: decode threads")
+    return parser.parse_args(argv)
+
+
+def main(argv=None):
+    return run(parse_args(argv))
 
 
 if __name__ == "__main__":

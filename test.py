@@ -14,7 +14,8 @@ on the host, gathered to rank 0 -> rank 0 evaluates, prints the metric lines and
 ``--out x.pkl`` pickles the per-image result dicts (mmdet ``DumpDetResults``).
 
 Additions: ``--text-bank FILE`` (a precomputed ``[K, 768]`` bank for the K class texts, ``.npy`` / ``.pt``: the XLM-R
-tokenizer files are not needed), ``--precision {fp32,fp16x3}``.  ``--show``, ``--show-dir`` and ``--tta`` are not
+tokenizer files are not needed), ``--precision {fp32,fp16x3}``, ``--loader {serial,stream}`` (``stream``: the streamed
+loader of wedetect_amd/stream.py — same predictions, decode / upload / steps overlapped) with ``--decode-workers N``.  ``--show``, ``--show-dir`` and ``--tta`` are not
 implemented and exit with a message.  A batch size above 1 may change predictions in the last bits (split-K choices
 of small batches).
 """
@@ -48,6 +49,10 @@ def parse_args(argv=None):
     parser.add_argument("--local_rank", "--local-rank", type=int, default=0)
     parser.add_argument("--text-bank", default=None, help="precomputed [K, 768] class embeddings (.npy / .pt)")
     parser.add_argument("--precision", default=None, choices=["fp32", "fp16x3"])
+    parser.add_argument("--loader", default="serial", choices=["serial", "stream"],
+                        help="serial: one image at a time through the pipeline (default); stream: decode threads, one batched "
+                             "pre-processing launch per batch, pipelined steps (YOLOWorldDetector.predict_stream)")
+    parser.add_argument("--decode-workers", type=int, default=None, help="--loader stream: decode threads (default min(12, $OMP_NUM_THREADS or 8))")
     args = parser.parse_args(argv)
     if "LOCAL_RANK" not in os.environ:
         os.environ["LOCAL_RANK"] = str(args.local_rank)
@@ -90,6 +95,17 @@ def predict_shard(model, dataset, indices, batch_size: int):
     return out
 
 
+def predict_shard_stream(model, dataset, indices, batch_size: int, decode_workers=None, stats=None):
+    """``predict_shard`` through the streamed loader: the same result dicts, in the same order."""
+    infos = [dataset.get_data_info(i) for i in indices]
+    out = []
+    for info, o in zip(infos, model.predict_stream(infos, batch_size, dataset.pipeline, decode_workers=decode_workers, stats=stats)):
+        p = o.pred_instances
+        out.append(dict(img_id=int(info["img_id"]), img_path=info.get("img_path"),
+                        pred_instances=dict(bboxes=p.bboxes.float(), scores=p.scores.float(), labels=p.labels.long())))
+    return out
+
+
 def main(argv=None):
     args = parse_args(argv)
     import torch
@@ -129,7 +145,10 @@ def main(argv=None):
     batch_size = int(cfg.test_dataloader.get("batch_size", 1))
     shard = parallel.shard_range(len(dataset), world, rank)
     t0 = time.time()
-    preds = predict_shard(model, dataset, shard, batch_size)
+    if args.loader == "stream":
+        preds = predict_shard_stream(model, dataset, shard, batch_size, args.decode_workers)
+    else:
+        preds = predict_shard(model, dataset, shard, batch_size)
     print(f"[rank {rank}] {len(preds)} images in {time.time() - t0:.1f} s", flush=True)
     preds = parallel.gather_to_rank0(preds)
     if rank == 0:

@@ -15,7 +15,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libwedetect_hip.so")
-SOURCES = ["abi.hip", "conv_gemm.hip", "similarity_grouped.hip", "split_gemm.hip", "split_gemm_pre.hip", "split_gemm_p8.hip", "split_gemm_p4.hip", "split_gemm_conv.hip", "split_gemm_conv3.hip", "split_gemm_mlp.hip", "split_gemm_mlpw.hip", "probe.hip", "stem.hip", "elementwise.hip", "preprocess.hip", "text.hip", "bricks.hip", "evaluate.hip", "det_eval.hip", "postprocess.hip"]
+SOURCES = ["abi.hip", "conv_gemm.hip", "similarity_grouped.hip", "split_gemm.hip", "split_gemm_pre.hip", "split_gemm_p8.hip", "split_gemm_p4.hip", "split_gemm_conv.hip", "split_gemm_conv3.hip", "split_gemm_mlp.hip", "split_gemm_mlpw.hip", "probe.hip", "stem.hip", "elementwise.hip", "preprocess.hip", "text.hip", "bricks.hip", "evaluate.hip", "det_eval.hip", "postprocess.hip", "feed.hip"]
+PUBLIC_HEADERS = ["wedetect_hip.h", "wedetect_hip_feed.h"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-inline-asm",
          "-I", os.path.join(ROOT, "include"), "-I", CSRC]
@@ -26,7 +27,7 @@ if os.environ.get("WD_DEBUG_ABLATIONS") == "1":          # timing-only ablation 
 
 
 def _headers():
-    return [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [os.path.join(ROOT, "include", "wedetect_hip.h")]
+    return [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + [os.path.join(ROOT, "include", h) for h in PUBLIC_HEADERS]
 
 
 def source_hash() -> str:
@@ -35,7 +36,7 @@ def source_hash() -> str:
     import hashlib
     h = hashlib.sha256()
     files = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h")))
-    for f in files + [os.path.join(ROOT, "include", "wedetect_hip.h")]:
+    for f in files + [os.path.join(ROOT, "include", h) for h in PUBLIC_HEADERS]:
         h.update(os.path.basename(f).encode())
         h.update(open(f, "rb").read())
     return h.hexdigest()
@@ -52,11 +53,13 @@ NO_SCRATCH = {"stem.hip": ["stem_fused_kernel"], "split_gemm_mlpw.hip": ["fused_
               "split_gemm_conv3.hip": ["split_conv3_kernel", "split_conv3w_kernel"],
               "split_gemm_pre.hip": ["split_gemm_pingpong_kernel", "split_gemm_glds_kernel"],
               "elementwise.hip": ["dwconv7_dma_kernel", "dwconv7_ln_reg4_dma_kernel"],
-              "similarity_grouped.hip": ["similarity_grouped_kernel"]}
+              "similarity_grouped.hip": ["similarity_grouped_kernel"],
+              "feed.hip": ["feed_resample_h_kernel", "feed_canvas_kernel"]}
 # (a source listed here with no kernel names gets the hazard scan and its NO_SCRATCH check only: similarity_grouped.hip has no
-# inline asm; its kernel is held to "no scratch" like the GEMM it is built from)
+# inline asm; its kernel is held to "no scratch" like the GEMM it is built from; feed.hip likewise: byte packing in registers)
 ASM_VMEM_SOURCES = {"split_gemm_mlpw.hip": ["fused_mlp_wide_kernel"], "split_gemm_mlp.hip": [], "split_gemm_p8.hip": [],
-                    "split_gemm_p4.hip": [], "split_gemm_pre.hip": [], "split_gemm_conv.hip": [], "split_gemm_conv3.hip": [], "stem.hip": [], "elementwise.hip": [], "similarity_grouped.hip": []}
+                    "split_gemm_p4.hip": [], "split_gemm_pre.hip": [], "split_gemm_conv.hip": [], "split_gemm_conv3.hip": [], "stem.hip": [], "elementwise.hip": [], "similarity_grouped.hip": [],
+                    "feed.hip": []}
 
 
 # kernels that issue ds_reads from inline asm (invisible to the compiler's waitcnt pass): scripts/check_asm_ds_reads.py

@@ -186,20 +186,24 @@ class _TowerHolder:
         tower.calibrate(images_u8, merge=True)
         self._share_scales(tower)
 
+    def calibrate_first(self, tower, images_u8) -> None:
+        """Before the first step of a tower (in line or streamed alike).  First batch of this CHECKPOINT: one fp32 pass
+        chooses the fp16x3 split scales for its activation ranges (engine.ImageTower.calibrate; scale 1 everywhere for
+        ordinary checkpoints); towers of other shapes adopt them."""
+        if not tower.calibrated and self.auto_calibrate:
+            if self.sscale is None:
+                tower.calibrate(images_u8)
+                self._share_scales(tower)
+            else:
+                tower.adopt_scales(self.sscale)
+
     def detect(self, tower, images_u8, text, meta, text_counts=None, **kw):
         """``tower.detect`` for the detector classes.  Small batches (the reference runs batch 1 everywhere) are
         launch-bound, so the step is replayed from a hipGraph captured on first use (engine.GraphedDetect: inputs are
         copied into the graph's static buffers, results are the tower's usual buffers — bit-identical to the eager
         step, tests/test_gpu_detector.py).  A graph belongs to one (tower, arithmetic mode, bank size, thresholds); the
         range guard's switch to fp32 therefore captures anew."""
-        if not tower.calibrated and self.auto_calibrate:
-            # first batch of this CHECKPOINT: one fp32 pass chooses the fp16x3 split scales for its activation ranges
-            # (engine.ImageTower.calibrate; scale 1 everywhere for ordinary checkpoints); towers of other shapes adopt them
-            if self.sscale is None:
-                tower.calibrate(images_u8)
-                self._share_scales(tower)
-            else:
-                tower.adopt_scales(self.sscale)
+        self.calibrate_first(tower, images_u8)
         if text.dim() == 3 or text_counts is not None:
             # one bank per image ([B, k_max, 768] + device counts): always the eager step, never captured — a graph would
             # have to own a static copy of every packed bank, and a batch of per-image banks is not launch-bound
@@ -370,6 +374,16 @@ class SimpleYOLOWorldDetector(_DeviceModule):
         # ImageTower.FALLBACK_RETRY clean batches it re-calibrates and returns to fp16x3, and so does the holder's default)
         self._h.precision = "fp32" if tower.overflowed else self._h._asked_precision
         return res, counts, tower
+
+    def predict_stream(self, images_or_paths: Sequence[Union[str, object]], batch_size: int, *, rescale: bool = True,
+                       with_embeddings: bool = True, decode_workers: Optional[int] = None, stats: Optional[dict] = None):
+        """``forward`` over a whole list of images as a stream of batches (wedetect_amd/stream.py): files are decoded by a
+        thread pool into pinned memory, a batch is letterboxed by ONE batched launch sequence (``wd_feed_batch_u8``), the
+        steps are pipelined and every batch's results come back in one packed copy.  Yields one dict per image, in input
+        order — the fields of ``forward`` as HOST tensors (``embeddings`` unless ``with_embeddings=False``).  ``stats``: a
+        dict that receives the stream's counters when it ends."""
+        from .stream import UniBackend, predict_stream
+        return predict_stream(UniBackend(self, rescale, with_embeddings), images_or_paths, batch_size, decode_workers, stats)
 
 
 # ------------------------------------------------------------------------------------------
@@ -555,6 +569,19 @@ def bank_pack_key(banks: Sequence[torch.Tensor]) -> Optional[Tuple[int, ...]]:
     if all(b is banks[0] for b in banks):
         return None
     return tuple(id(b) for b in banks)
+
+
+def letterbox_meta(m: dict, hh: int, ww: int, rescale: bool) -> List[float]:
+    """The post-process's 8 floats of one image from its sample's metainfo (``pad_param``, ``scale_factor``,
+    ``ori_shape``; an [hh, ww] input that was never letterboxed when they are missing)."""
+    ori = m.get("ori_shape", (hh, ww))
+    sf = m.get("scale_factor", (1.0, 1.0))
+    pad = m.get("pad_param", None)
+    px, py = (0.0, 0.0) if pad is None else (float(pad[2]), float(pad[0]))
+    sx, sy = (float(sf[0]), float(sf[1])) if rescale else (1.0, 1.0)
+    if not rescale:
+        px = py = 0.0
+    return [px, py, 0.0, sx, sy, float(ori[1]), float(ori[0]), 1.0]
 
 
 def pack_image_banks(banks: Sequence[torch.Tensor], device=None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -810,15 +837,7 @@ class YOLOWorldDetector(_DeviceModule):
         L.chw_to_hwc_u8(chw, x)                              # bgr_to_rgb + NHWC (data_preprocessor.py:35-36)
         metas = []
         for i in idxs:
-            m = _meta_of(samples[i])
-            ori = m.get("ori_shape", (hh, ww))
-            sf = m.get("scale_factor", (1.0, 1.0))
-            pad = m.get("pad_param", None)
-            px, py = (0.0, 0.0) if pad is None else (float(pad[2]), float(pad[0]))
-            sx, sy = (float(sf[0]), float(sf[1])) if rescale else (1.0, 1.0)
-            if not rescale:
-                px = py = 0.0
-            metas.append([px, py, 0.0, sx, sy, float(ori[1]), float(ori[0]), 1.0])
+            metas.append(letterbox_meta(_meta_of(samples[i]), hh, ww, rescale))
         tower = self._h.tower(len(idxs), hh, ww)
         meta = torch.tensor(metas, dtype=torch.float32, device=dev)
         if packed is None:
@@ -844,6 +863,18 @@ class YOLOWorldDetector(_DeviceModule):
             s.pred_instances = inst
             out[i] = s
         return out
+
+    def predict_stream(self, data_infos: Sequence[dict], batch_size: int, pipeline_cfg, *, rescale: bool = True,
+                       decode_workers: Optional[int] = None, stats: Optional[dict] = None):
+        """``predict`` over a whole list of data infos (``dataset.get_data_info(i)``: ``img_path``, ``img_id``, optionally
+        ``texts``) as a stream of batches (wedetect_amd/stream.py).  ``pipeline_cfg``: the test pipeline (the config's list
+        of dicts or a ``Compose``) — it must have the shipped shape (LoadImageFromFile, WeDetectKeepRatioResize,
+        WeDetectLetterResize, LoadAnnotations, LoadText, PackDetInputs); its geometry code runs as it is, its pixel work is
+        replaced by ONE batched launch sequence per batch.  Yields one ``DetDataSample`` per image, in input order, each
+        exactly once; ``pred_instances`` holds what ``predict`` fills, as HOST tensors.  ``stats``: a dict that receives
+        the stream's counters when it ends."""
+        from .stream import MmdetBackend, predict_stream
+        return predict_stream(MmdetBackend(self, pipeline_cfg, rescale), data_infos, batch_size, decode_workers, stats)
 
 
 MODELS.register_module(module=YOLOWorldDetector)

@@ -251,8 +251,12 @@ class WeDetectLetterResize:
         self.allow_scale_up = allow_scale_up
         self._plans: Optional[_PlanCache] = None
 
-    def __call__(self, results: dict) -> dict:
-        img = results["img"]
+    def geometry(self, results: dict, src_hw: Tuple[int, int]) -> dict:
+        """The letter step without its launch: consumes ``_pending_resize``, updates ``scale_factor``, ``img_shape`` and
+        ``pad_param`` in ``results`` exactly as ``__call__`` does, and returns what the resample needs — ``dh, dw, interp``
+        (target size and interpolation of the ONE fused resample from the ``src_hw`` source image), ``canvas`` (h, w),
+        ``top, left`` and ``pad_val``.  ``__call__`` launches it per image; the streamed loader (wedetect_amd/stream.py)
+        turns it into a descriptor of the batched feed."""
         if "batch_shape" in results:
             sh, sw = (int(v) for v in results["batch_shape"])                        # :186-187
         else:
@@ -275,13 +279,19 @@ class WeDetectLetterResize:
             scale_factor = (scale_factor[0] * o[0], scale_factor[1] * o[1])
         results["scale_factor"] = scale_factor
         top, left = int(round(pad_h // 2 - 0.1)), int(round(pad_w // 2 - 0.1))       # :235-236
+        dh, dw, interp = pending if pending is not None else (int(src_hw[0]), int(src_hw[1]), "area")
+        results["img_shape"] = (sh, sw, 3)                                           # :260 (image.shape)
+        results["pad_param"] = np.array([top, pad_h - top, left, pad_w - left], dtype=np.float32)
+        return dict(dh=dh, dw=dw, interp=interp, canvas=(sh, sw), top=top, left=left, pad_val=self.pad_val)
+
+    def __call__(self, results: dict) -> dict:
+        img = results["img"]
+        g = self.geometry(results, (int(img.shape[0]), int(img.shape[1])))
         dev = img.device
         if self._plans is None or self._plans.dev != dev:
             self._plans = _PlanCache(dev)
-        dh, dw, interp = pending if pending is not None else (int(img.shape[0]), int(img.shape[1]), "area")
-        results["img"] = cv_resize_pad(img, dh, dw, interp, (sh, sw), top, left, self.pad_val, plans=self._plans)
-        results["img_shape"] = (sh, sw, 3)                                           # :260 (image.shape)
-        results["pad_param"] = np.array([top, pad_h - top, left, pad_w - left], dtype=np.float32)
+        results["img"] = cv_resize_pad(img, g["dh"], g["dw"], g["interp"], g["canvas"], g["top"], g["left"], self.pad_val,
+                                       plans=self._plans)
         return results
 
 
@@ -323,15 +333,19 @@ class PackDetInputs:
     def __init__(self, meta_keys: Sequence[str] = DEFAULT_KEYS):
         self.meta_keys = tuple(meta_keys)
 
-    def __call__(self, results: dict) -> dict:
-        img = results["img"]
-        if isinstance(img, np.ndarray):
-            img = torch.from_numpy(np.ascontiguousarray(img))
+    def sample(self, results: dict) -> DetDataSample:
+        """The data sample alone (the listed ``meta_keys``), for callers that keep the pixels elsewhere."""
         meta = {}
         for k in self.meta_keys:
             if k in results:
                 meta[k] = results[k]
-        return dict(inputs=img.permute(2, 0, 1), data_samples=DetDataSample(metainfo=meta))
+        return DetDataSample(metainfo=meta)
+
+    def __call__(self, results: dict) -> dict:
+        img = results["img"]
+        if isinstance(img, np.ndarray):
+            img = torch.from_numpy(np.ascontiguousarray(img))
+        return dict(inputs=img.permute(2, 0, 1), data_samples=self.sample(results))
 
 
 class Compose:
