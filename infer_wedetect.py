@@ -10,7 +10,10 @@ annotated copy in ``--output-dir``.  Everything numeric runs through libwedetect
 
 Additions (absent from the reference, all optional): ``--text-bank FILE`` loads a precomputed ``[K + 1, 768]`` class
 bank (``.npy`` / ``.pt``; rows for the K prompts then the blank) instead of running the text tower — for hosts without
-the XLM-R tokenizer files; ``--precision {fp32,fp16x3}``; ``--dump-json`` also writes the kept detections per image.
+the XLM-R tokenizer files; ``--precision {fp32,fp16x3}``; ``--dump-json`` also writes the kept detections per image;
+``--tile N`` (default 0 = off) runs every image through ``YOLOWorldDetector.predict_tiled`` — overlapping N x N crops
+(``--tile-overlap``, ``--tile-batch`` tiles per step, ``--edge-margin``) plus one overview of the whole image
+(``--no-overview``), merged on the device — before the same ``--threshold`` / ``--topk`` filter.
 """
 import argparse
 import json
@@ -47,6 +50,12 @@ def parse_args(argv=None):
     parser.add_argument("--text-bank", default=None, help="precomputed [K+1, 768] class embeddings (.npy / .pt)")
     parser.add_argument("--precision", default=None, choices=["fp32", "fp16x3"])
     parser.add_argument("--dump-json", action="store_true", help="write <image>.json with the kept detections")
+    parser.add_argument("--tile", default=0, type=int, help="tiled inference on overlapping N x N crops (a multiple of 32); 0 = off")
+    parser.add_argument("--tile-overlap", default=0.2, type=float, help="overlap of neighbouring tiles, 0 .. 0.5 of the tile")
+    parser.add_argument("--tile-batch", default=32, type=int, help="tiles per tower step")
+    parser.add_argument("--no-overview", action="store_true", help="no letterboxed overview of the whole image beside the crops")
+    parser.add_argument("--edge-margin", default=2.0, type=float,
+                        help="drop rows closer than this many pixels to an interior side of their crop")
     return parser.parse_args(argv)
 
 
@@ -94,6 +103,19 @@ def visualize(output_file, image_path, bboxes, labels):
     image.save(output_file)
 
 
+def tiled_detections(model, image_path, texts, args):
+    """``--tile N``: the image through ``predict_tiled``, then the filter of ``inference_detector`` (score, top-k)."""
+    from PIL import Image, ImageOps
+    with Image.open(image_path) as im:
+        rgb = np.asarray(ImageOps.exif_transpose(im).convert("RGB"))
+    pred = model.predict_tiled(rgb, texts, tile=(args.tile, args.tile), overlap=args.tile_overlap, overview=not args.no_overview,
+                               tile_batch=args.tile_batch, edge_margin=args.edge_margin).pred_instances
+    pred = pred[pred.scores.float() > args.threshold]
+    if len(pred.scores) > args.topk:
+        pred = pred[pred.scores.float().topk(args.topk)[1]]
+    return pred.cpu().numpy()
+
+
 def main(argv=None, tokenizer=None):
     args = parse_args(argv)
     cfg = Config.fromfile(args.config)
@@ -117,7 +139,10 @@ def main(argv=None, tokenizer=None):
         model.reparameterize(texts)
     results = []
     for n, image_path in enumerate(images):
-        pred = inference_detector(model, image_path, texts, test_pipeline, args.topk, args.threshold)
+        if args.tile > 0:
+            pred = tiled_detections(model, image_path, texts, args)
+        else:
+            pred = inference_detector(model, image_path, texts, test_pipeline, args.topk, args.threshold)
         labels = [f"{texts[c][0]} {s:0.2f}" for c, s in zip(pred["labels"], pred["scores"])]
         out = osp.join(args.output_dir, osp.basename(image_path))
         visualize(out, image_path, pred["bboxes"], labels)

@@ -876,6 +876,198 @@ class YOLOWorldDetector(_DeviceModule):
         from .stream import MmdetBackend, predict_stream
         return predict_stream(MmdetBackend(self, pipeline_cfg, rescale), data_infos, batch_size, decode_workers, stats)
 
+    # -- tiled inference --------------------------------------------------------------------
+    def _step_kw(self) -> dict:
+        cfg = self.test_cfg
+        return dict(normalize_text=True, score_thr=cfg["score_thr"], iou_thr=cfg["nms"]["iou_threshold"], with_embed=False,
+                    nms="mmcv", nms_param=int(cfg["nms"].get("split_thr", 10000)))
+
+    @torch.no_grad()
+    def predict_tiled(self, image, texts=None, *, tile=None, overlap: float = 0.2, overview: bool = True, tile_batch: int = 32,
+                      edge_margin: float = 2.0, merge_iou: Optional[float] = None, max_per_img: Optional[int] = None,
+                      channel_order: str = "rgb", stats: Optional[dict] = None) -> "DetDataSample":
+        """One LARGE image at the network's own resolution: cut into overlapping ``tile``-sized crops (+ one overview of the
+        whole image through the test pipeline's geometry), detected as batches of ``tile_batch`` tiles, merged on the device
+        (wedetect_amd/tiling.py, include/wedetect_hip_tile.h):
+
+            upload (image, plan + metadata) -> ONE cut launch (+ the overview's resize) -> pipelined tower steps
+            (``detect(overlap_post=True)``; each step's rows are copied into stacked buffers on the post stream) -> ONE merge
+            (border drop, translate, sort, mmcv-form NMS over all tiles) -> ONE download (rows, count, range flags)
+
+        ``image``: HWC uint8 (ndarray / tensor, host or device) or a PIL image, channels in ``channel_order`` ("rgb" / "bgr").
+        ``texts``: a class list ``[[a], [b], ...]`` (None: the bank of ``reparameterize`` / ``set_text_embeddings``).
+        ``tile`` (h, w), None = ``img_scale``; ``merge_iou`` None = ``test_cfg.nms.iou_threshold``; ``max_per_img`` None =
+        ``test_cfg.max_per_img``; ``edge_margin``: rows closer than this to an INTERIOR side of their crop are dropped (the
+        object is cut there and lies whole in a neighbouring crop or in the overview).  A remainder of r tiles runs on the
+        tower of the next power of two >= r, padded with blank tiles.  An image that fits one tile goes through ``predict``.
+
+        The pipelined steps only DETECT a trip of the fp16x3 range guard (a flag, or a count of -1, arrives with the
+        download); the image is then run again step by step in line through ``checked_counts``, which owns the guard's logic,
+        as wedetect_amd/stream.py does.  Returns a ``DetDataSample`` whose ``pred_instances`` holds HOST tensors: ``bboxes``
+        (image pixels), ``scores``, ``labels`` and ``tiles`` (the plan index of the tile each row came from)."""
+        from . import lib as L
+        from . import tile as T
+        from . import tiling as G
+        from .pipeline import cv_resize_pad
+        dev = self._h.device
+        if dev is None:
+            raise RuntimeError("model is not on a HIP device: call .cuda()")
+        if channel_order not in ("rgb", "bgr"):
+            raise ValueError("channel_order must be 'rgb' or 'bgr'")
+        swap = channel_order == "bgr"                        # the tower reads RGB
+        if hasattr(image, "convert") and not isinstance(image, (np.ndarray, torch.Tensor)):
+            image = np.asarray(image.convert("RGB"))
+        img = torch.from_numpy(np.ascontiguousarray(image)) if isinstance(image, np.ndarray) else image
+        if not isinstance(img, torch.Tensor) or img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3:
+            raise TypeError("image must be uint8 HxWx3")
+        H, W = int(img.shape[0]), int(img.shape[1])
+        th, tw = (int(v) for v in (tile if tile is not None else self.img_scale))
+        max_out = int(max_per_img if max_per_img is not None else self.test_cfg["max_per_img"])
+        if not 1 <= max_out <= T.MERGE_MAX_OUT:
+            raise NotImplementedError(f"max_per_img {max_out} outside 1 .. {T.MERGE_MAX_OUT} (the NMS kernel's kept-list capacity)")
+        iou = float(merge_iou if merge_iou is not None else self.test_cfg["nms"]["iou_threshold"])
+        if not float(edge_margin) >= 0.0:
+            raise ValueError("edge_margin must be >= 0")
+        plan = G.plan_tiles(H, W, (th, tw), overlap, overview)
+        sample = DetDataSample(metainfo=dict(ori_shape=(H, W), img_shape=(H, W)))
+        if texts is not None:
+            sample.set_metainfo(dict(texts=texts))
+        bank = self._bank_for(sample).to(dev)
+        if stats is not None:
+            stats.update(tiles=len(plan), crops=G.n_crops(plan), steps=0, trips=0, inline=False, d2h_copies=0)
+        img_dev = img.to(dev, non_blocking=True).contiguous()
+        if G.fits_one_tile(plan):
+            # the plain step: the image through the test pipeline's geometry, then ``predict``
+            g = G.overview_geometry(H, W, (th, tw))
+            canvas = cv_resize_pad(img_dev, g["dh"], g["dw"], g["interp"], (th, tw), g["top"], g["left"], g["pad_val"], swap_rb=not swap)
+            sample.set_metainfo(dict(scale_factor=g["scale_factor"], pad_param=g["pad_param"], img_shape=(th, tw, 3)))
+            return self.predict([canvas.permute(2, 0, 1).contiguous()], [sample])[0]          # predict takes CHW BGR
+        h = self._h
+        steps = G.step_sizes(len(plan), tile_batch)
+        total = sum(b for _, b in steps)
+        max_in = h.max_out
+        if total * max_in > T.MERGE_MAX_ROWS:
+            raise NotImplementedError(f"{total} tiles x {max_in} rows per tile exceed the merge's {T.MERGE_MAX_ROWS} rows: use larger "
+                                      "tiles, less overlap or a smaller test_cfg.max_per_img")
+        plan_p = G.pad_plan(plan, total)
+        og = G.overview_geometry(H, W, (th, tw)) if bool((plan["kind"] == G.OVERVIEW).any()) else None
+        meta_host = G.tile_meta(plan_p, (th, tw), None if og is None else og["meta"])
+        # ONE control block: descriptors, then the per-tile metadata at a 256-byte boundary
+        meta_off = (total * T.TILE_DTYPE.itemsize + 255) // 256 * 256
+        B = self._tiled_buffers(total, max_in, th, tw, max_out, len(steps), dev)
+        ctl_np = B["ctl_pin"].numpy()                        # the previous call ended with a synchronisation: free to rewrite
+        ctl_np[: total * T.TILE_DTYPE.itemsize] = plan_p.view(np.uint8)
+        ctl_np[meta_off: meta_off + total * 32] = meta_host.view(np.uint8).reshape(-1)
+        ctl = B["ctl"]
+        ctl.copy_(B["ctl_pin"], non_blocking=True)
+        meta = ctl[meta_off: meta_off + total * 32].view(torch.float32).view(total, 8)
+        tiles = B["tiles"]
+        T.tile_cut_u8(img_dev, ctl.data_ptr(), plan_p, tiles, fill=114, swap_rb=swap)
+        if og is not None:
+            k = int(np.nonzero(plan_p["kind"] == G.OVERVIEW)[0][0])
+            cv_resize_pad(img_dev, og["dh"], og["dw"], og["interp"], (th, tw), og["top"], og["left"], og["pad_val"], swap_rb=swap,
+                          out=tiles[k])
+        kw = self._step_kw()
+        n_cls = int(bank.shape[0])
+        split_thr = int(self.test_cfg["nms"].get("split_thr", 10000))
+        towers = [h.tower(b, th, tw) for _, b in steps]
+        main = torch.cuda.current_stream()
+
+        def stack(res, tower, i, lo, b):
+            B["boxes"][lo:lo + b].copy_(res["bboxes"], non_blocking=True)
+            B["scores"][lo:lo + b].copy_(res["scores"], non_blocking=True)
+            B["labels"][lo:lo + b].copy_(res["labels"], non_blocking=True)
+            B["counts"][lo:lo + b].copy_(res["count"], non_blocking=True)
+            B["flags"][i].copy_(tower.range_flags, non_blocking=True)
+
+        def merge_and_download():
+            T.tile_merge(B["boxes"], B["scores"], B["labels"], B["counts"], ctl.data_ptr(), total, max_in, n_cls, float(edge_margin),
+                         iou, split_thr, max_out, B["out_boxes"], B["out_scores"], B["out_labels"], B["out_src"], B["out_count"], B["ws"])
+            B["pin"].copy_(B["stage"], non_blocking=True)    # ONE packed D2H: rows, count, range flags
+            torch.cuda.current_stream().synchronize()
+            if stats is not None:
+                stats["d2h_copies"] += 1
+            return {k: v.clone() for k, v in B["host"].items()}
+
+        inline = any(t.overflowed for t in h._towers.values())       # a tower in its fp32 fallback: every step goes in line
+        host = None
+        if not inline:
+            lo = 0
+            for i, ((_, b), tower) in enumerate(zip(steps, towers)):
+                x = tiles[lo:lo + b]
+                h.calibrate_first(tower, x)
+                res = tower.detect(x, bank, meta[lo:lo + b], overlap_post=True, **kw)
+                with torch.cuda.stream(tower.post_stream):   # before the next post-process overwrites the tower's rows
+                    stack(res, tower, i, lo, b)
+                    B["events"][i].record(tower.post_stream)
+                lo += b
+            for i in range(len(steps)):
+                main.wait_event(B["events"][i])
+            host = merge_and_download()
+            if stats is not None:
+                stats["steps"] += len(steps)
+            fl = [f for (tower, row) in zip(towers, host["flags"].tolist()) if tower.precision == "fp16x3" for f in row]
+            if int(host["count"]) < 0 or any(fl):
+                inline = True
+                if stats is not None:
+                    stats["trips"] += 1
+        if inline:
+            torch.cuda.synchronize(dev)
+            for tower in set(towers):
+                tower.range_flags.zero_()                    # a discarded step may have raised them
+            lo = 0
+            for i, ((_, b), tower) in enumerate(zip(steps, towers)):
+                x, m = tiles[lo:lo + b], meta[lo:lo + b]
+                run = lambda: h.detect(tower, x, bank, m, **kw)
+                res = run()
+                recal = (lambda: h.recalibrate(tower, x)) if h.auto_calibrate else None
+                tower.checked_counts(res, run, recal)
+                h.precision = "fp32" if tower.overflowed else h._asked_precision
+                stack(res, tower, i, lo, b)
+                lo += b
+            B["flags"].zero_()
+            host = merge_and_download()
+            if stats is not None:
+                stats["steps"] += len(steps)
+                stats["inline"] = True
+            if int(host["count"]) < 0:
+                raise RuntimeError("non-finite scores survived the in-line range guard")
+        n = int(host["count"])
+        sample.pred_instances = InstanceData(bboxes=host["boxes"][:n], scores=host["scores"][:n], labels=host["labels"][:n].to(torch.int64),
+                                             tiles=(host["src"][:n] // max_in).to(torch.int64))
+        return sample
+
+    def _tiled_buffers(self, total: int, max_in: int, th: int, tw: int, max_out: int, n_steps: int, dev) -> dict:
+        """Device buffers of ``predict_tiled`` for one geometry, kept between calls: the tiles, the stacked per-tile rows, the
+        merge's workspace, and ONE staging blob (merged rows, count, range flags per step) with its pinned twin."""
+        from . import tile as T
+        key = (total, max_in, th, tw, max_out, n_steps, str(dev))
+        B = getattr(self, "_tiled", None)
+        if B is not None and B["key"] == key:
+            return B
+        f32, i32, u8 = torch.float32, torch.int32, torch.uint8
+        e = lambda *s, dt=f32: torch.empty(*s, dtype=dt, device=dev)
+        B = dict(key=key, tiles=e(total, th, tw, 3, dt=u8), boxes=e(total, max_in, 4), scores=e(total, max_in),
+                 labels=e(total, max_in, dt=i32), counts=e(total, dt=i32),
+                 ws=e(T.merge_workspace_bytes(total, max_in), dt=u8), events=[torch.cuda.Event() for _ in range(n_steps)])
+        ctl_bytes = (total * T.TILE_DTYPE.itemsize + 255) // 256 * 256 + total * 32      # descriptors | per-tile metadata
+        B["ctl"], B["ctl_pin"] = e(ctl_bytes, dt=u8), torch.zeros(ctl_bytes, dtype=u8).pin_memory()
+        parts = (("boxes", (max_out, 4), f32), ("scores", (max_out,), f32), ("labels", (max_out,), i32), ("src", (max_out,), i32),
+                 ("count", (1,), i32), ("flags", (n_steps, 2), i32))
+        off, lay = 0, []
+        for name, shape, dt in parts:
+            nb = int(np.prod(shape)) * 4
+            lay.append((name, shape, dt, off, nb))
+            off += (nb + 255) // 256 * 256
+        B["stage"] = torch.zeros(off, dtype=u8, device=dev)
+        B["pin"] = torch.zeros(off, dtype=u8).pin_memory()
+        B["host"] = {}
+        for name, shape, dt, o, nb in lay:
+            B["out_" + name if name != "flags" else "flags"] = B["stage"][o:o + nb].view(dt).view(shape)
+            B["host"][name] = B["pin"][o:o + nb].view(dt).view(shape)
+        self._tiled = B
+        return B
+
 
 MODELS.register_module(module=YOLOWorldDetector)
 MODELS.register_module(module=MultiModalYOLOBackbone)
