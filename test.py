@@ -15,8 +15,9 @@ on the host, gathered to rank 0 -> rank 0 evaluates, prints the metric lines and
 
 Additions: ``--text-bank FILE`` (a precomputed ``[K, 768]`` bank for the K class texts, ``.npy`` / ``.pt``: the XLM-R
 tokenizer files are not needed), ``--precision {fp32,fp16x3}``, ``--loader {serial,stream}`` (``stream``: the streamed
-loader of wedetect_amd/stream.py — same predictions, decode / upload / steps overlapped) with ``--decode-workers N``.  ``--show``, ``--show-dir`` and ``--tta`` are not
-implemented and exit with a message.  A batch size above 1 may change predictions in the last bits (split-K choices
+loader of wedetect_amd/stream.py — same predictions, decode / upload / steps overlapped) with ``--decode-workers N``, ``--aug-test`` (test-time augmentation: the reference's ``--tta`` block — ``cfg.tta_model`` /
+``cfg.tta_pipeline`` or its flip defaults — through wedetect_amd/tta.py; views merged on the device).  ``--show``, ``--show-dir``
+and ``--tta`` itself are not implemented and exit with a message.  A batch size above 1 may change predictions in the last bits (split-K choices
 of small batches).
 """
 import argparse
@@ -45,7 +46,9 @@ def parse_args(argv=None):
                         help="override some settings in the used config, the key-value pair in xxx=yyy format will be "
                              "merged into config file.")
     parser.add_argument("--launcher", choices=["none", "pytorch", "slurm", "mpi"], default="none", help="job launcher")
-    parser.add_argument("--tta", action="store_true", help="test time augmentation (not implemented)")
+    parser.add_argument("--tta", action="store_true", help="test time augmentation (not implemented under this name: see --aug-test)")
+    parser.add_argument("--aug-test", action="store_true",
+                        help="test-time augmentation: cfg.tta_model / cfg.tta_pipeline, or flip + plain merged with NMS 0.5, 100 per image")
     parser.add_argument("--local_rank", "--local-rank", type=int, default=0)
     parser.add_argument("--text-bank", default=None, help="precomputed [K, 768] class embeddings (.npy / .pt)")
     parser.add_argument("--precision", default=None, choices=["fp32", "fp16x3"])
@@ -56,10 +59,13 @@ def parse_args(argv=None):
     args = parser.parse_args(argv)
     if "LOCAL_RANK" not in os.environ:
         os.environ["LOCAL_RANK"] = str(args.local_rank)
-    for flag, on in (("--show", args.show), ("--show-dir", args.show_dir), ("--tta", args.tta)):
+    for flag, on in (("--show", args.show), ("--show-dir", args.show_dir)):
         if on:
-            parser.exit(2, f"test.py: {flag} is not implemented on this path (visualisation and flip TTA are out of "
-                           f"scope); run without it\n")
+            parser.exit(2, f"test.py: {flag} is not implemented on this path (visualisation is out of scope); run without it\n")
+    if args.tta:
+        parser.exit(2, "test.py: --tta is not implemented under this name; test-time augmentation is --aug-test\n")
+    if args.aug_test and args.loader == "stream":
+        parser.exit(2, "test.py: --aug-test runs with --loader serial only (the streamed loader has no view branches)\n")
     if args.launcher in ("slurm", "mpi"):
         parser.exit(2, f"test.py: --launcher {args.launcher} is not implemented; use --launcher pytorch (dist_test.sh)\n")
     if args.out is not None and not args.out.endswith((".pkl", ".pickle")):
@@ -92,6 +98,44 @@ def predict_shard(model, dataset, indices, batch_size: int):
             out.append(dict(img_id=int(info["img_id"]), img_path=info.get("img_path"),
                             pred_instances=dict(bboxes=p.bboxes.detach().float().cpu(), scores=p.scores.detach().float().cpu(),
                                                 labels=p.labels.detach().long().cpu())))
+    return out
+
+
+def build_tta(cfg):
+    """The reference's ``--tta`` block (test.py:94-127): ``cfg.tta_model`` / ``cfg.tta_pipeline`` when the config has them,
+    its defaults otherwise (wedetect_amd/tta.py).  -> (tta_model dict without ``module``, tta_pipeline list)."""
+    import warnings
+    from wedetect_amd import tta
+    tta_model, tta_pipeline = cfg.get("tta_model", None), cfg.get("tta_pipeline", None)
+    if tta_model is None:
+        warnings.warn("Cannot find ``tta_model`` in config, we will set it as default.")
+        tta_model = dict(tta.DEFAULT_TTA_MODEL)
+    if tta_pipeline is None:
+        warnings.warn("Cannot find ``tta_pipeline`` in config, we will set it as default.")
+        data_cfg = cfg.test_dataloader.dataset                # the reference descends to the innermost dataset; the shipped
+        test_pipeline = data_cfg.get("pipeline", None)        # configs keep the pipeline on the MultiModalDataset wrapper
+        while "dataset" in data_cfg:
+            data_cfg = data_cfg["dataset"]
+            test_pipeline = data_cfg.get("pipeline", test_pipeline)
+        if test_pipeline is None:
+            raise SystemExit("--aug-test: the test dataset has no pipeline to derive the TTA pipeline from")
+        tta_pipeline = tta.default_tta_pipeline(test_pipeline)
+    return dict(tta_model), list(tta_pipeline)
+
+
+def predict_shard_tta(tta_model, dataset, pipeline, indices, batch_size: int):
+    """``predict_shard`` under test-time augmentation: ``pipeline`` ends in a ``TestTimeAug`` (every image comes out as a list
+    of views); a batch is collated per view (``tta.collate_views``) and goes through ``DetTTAModel.test_step``."""
+    from wedetect_amd.tta import collate_views
+    out = []
+    idx = list(indices)
+    for lo in range(0, len(idx), batch_size):
+        infos = [dataset.get_data_info(i) for i in idx[lo:lo + batch_size]]
+        outputs = tta_model.test_step(collate_views([pipeline(dict(info)) for info in infos]))
+        for info, o in zip(infos, outputs):
+            p = o.pred_instances
+            out.append(dict(img_id=int(info["img_id"]), img_path=info.get("img_path"),
+                            pred_instances=dict(bboxes=p.bboxes.float(), scores=p.scores.float(), labels=p.labels.long())))
     return out
 
 
@@ -145,7 +189,12 @@ def main(argv=None):
     batch_size = int(cfg.test_dataloader.get("batch_size", 1))
     shard = parallel.shard_range(len(dataset), world, rank)
     t0 = time.time()
-    if args.loader == "stream":
+    if args.aug_test:
+        from wedetect_amd.pipeline import Compose
+        from wedetect_amd.registry import MODELS
+        tta_model, tta_pipeline = build_tta(cfg)
+        preds = predict_shard_tta(MODELS.build(dict(tta_model, module=model)), dataset, Compose(tta_pipeline), shard, batch_size)
+    elif args.loader == "stream":
         preds = predict_shard_stream(model, dataset, shard, batch_size, args.decode_workers)
     else:
         preds = predict_shard(model, dataset, shard, batch_size)

@@ -17,6 +17,7 @@ import torch
 
 from . import config as _config  # noqa: F401  (fills the registries)
 from . import pipeline as _pipeline  # noqa: F401
+from . import tta as _tta  # noqa: F401
 from .cfgfile import Config
 from .detector import InstanceData
 from .pipeline import Compose

@@ -1068,6 +1068,193 @@ class YOLOWorldDetector(_DeviceModule):
         self._tiled = B
         return B
 
+    # -- test-time augmentation -------------------------------------------------------------
+    @torch.no_grad()
+    def predict_views(self, views, tta_cfg: dict, rescale: bool = True, stats: Optional[dict] = None) -> List["DetDataSample"]:
+        """Test-time augmentation of one batch (mmdet ``DetTTAModel``; wedetect_amd/tta.py, include/wedetect_hip_views.h).
+        ``views``: a list of ``(batch_inputs, batch_data_samples)`` as ``predict`` takes them, one per view, all of the same B
+        images in the same order; a view's samples say how it was flipped (``flip`` / ``flip_direction``).  Every view has one
+        input shape; at most 4 distinct shapes (the towers kept per shape).  ``tta_cfg``:
+        ``dict(nms=dict(type='nms', iou_threshold=...[, split_thr]), max_per_img=...)``.
+
+            one pipelined tower step per view (``detect(overlap_post=True)`` with ``predict``'s keywords, per-image banks
+            included; each step's rows are copied into stacked [V, B, max_in] buffers on the post stream) -> ONE merge
+            (``wd_views_merge``: un-flip, sort, mmcv-form NMS per image over all views) -> ONE download (rows, counts, flags)
+
+        The pipelined steps only DETECT a trip of the fp16x3 range guard, as in ``predict_tiled``: the views are then run again
+        in line through ``checked_counts`` and merged again.  Returns the FIRST view's sample of every image (mmdet
+        ``_merge_single_sample``); ``pred_instances`` holds HOST tensors: ``bboxes`` (original-image pixels), ``scores``,
+        ``labels`` and ``views`` (the view each row came from)."""
+        from . import lib as L
+        from . import views as VW
+        from .tta import check_tta_cfg
+        h = self._h
+        dev = h.device
+        if dev is None:
+            raise RuntimeError("model is not on a HIP device: call .cuda()")
+        cfg = check_tta_cfg(tta_cfg)
+        views = [(list(x for x in inp), list(smp) if smp is not None else [None] * len(inp)) for inp, smp in views]
+        V = len(views)
+        if not 1 <= V <= VW.MERGE_MAX_VIEWS:
+            raise NotImplementedError(f"{V} views: 1 .. {VW.MERGE_MAX_VIEWS} are supported")
+        B = len(views[0][0])
+        max_in, max_out = h.max_out, cfg["max_per_img"]
+        if V * max_in > VW.MERGE_MAX_ROWS:
+            raise NotImplementedError(f"{V} views x {max_in} rows per view exceed the merge's {VW.MERGE_MAX_ROWS} rows per image: use "
+                                      "fewer views or a smaller test_cfg.max_per_img")
+        shapes, flips, banks_v = [], [], []
+        for v, (xs, samples) in enumerate(views):
+            if len(xs) != B or len(samples) != B or B < 1:
+                raise ValueError(f"view {v}: {len(xs)} inputs and {len(samples)} data samples, but view 0 has {B} images")
+            shp = {tuple(t.shape) for t in xs}
+            if len(shp) != 1 or len(next(iter(shp))) != 3 or next(iter(shp))[0] != 3:
+                raise ValueError(f"view {v}: inputs must be [3, H, W] tensors of one shape after the test pipeline, got {sorted(shp)}")
+            _, hh, ww = next(iter(shp))
+            if hh % 32 or ww % 32:
+                raise ValueError(f"view {v}: input size {hh}x{ww} is not a multiple of 32 (letterbox to img_scale first)")
+            shapes.append((int(hh), int(ww)))
+            codes = set()
+            for s in samples:
+                m = _meta_of(s)
+                d = m.get("flip_direction") if m.get("flip") else None
+                if d not in VW.FLIP_CODES:
+                    raise ValueError(f"view {v}: flip_direction {d!r}")
+                codes.add(VW.FLIP_CODES[d])
+            if len(codes) != 1:
+                raise ValueError(f"view {v}: its samples disagree about the flip ({sorted(codes)}); a view is one augmentation of the batch")
+            flips.append(codes.pop())
+            banks_v.append([self._bank_for(s) for s in samples])
+        if len(set(shapes)) > 4:
+            raise NotImplementedError(f"{len(set(shapes))} distinct input shapes: at most 4 (one tower is kept per shape)")
+        n_cls = max(int(b.shape[0]) for banks in banks_v for b in banks)
+        iou, split_thr = cfg["nms"]["iou_threshold"], int(cfg["nms"].get("split_thr", 10000))
+        Bf = self._views_buffers(V, B, max_in, max_out, tuple(shapes), dev)
+        ctl = Bf["ctl_host"]                                 # the previous call ended with a synchronisation: free to rewrite
+        ctl["flip"][:] = torch.tensor(flips, dtype=torch.int32)
+        for b, s in enumerate(views[0][1]):
+            ori = _meta_of(s).get("ori_shape", shapes[0])
+            ctl["wh"][b, 0], ctl["wh"][b, 1] = float(ori[1]), float(ori[0])
+        for v, (_, samples) in enumerate(views):
+            ctl["meta"][v] = torch.tensor([letterbox_meta(_meta_of(s), shapes[v][0], shapes[v][1], rescale) for s in samples],
+                                          dtype=torch.float32)
+        Bf["ctl"].copy_(Bf["ctl_pin"], non_blocking=True)
+        kw = self._step_kw()
+        towers = [h.tower(B, hh, ww) for hh, ww in shapes]
+        packed = [self._packed_for(banks, dev) for banks in banks_v]
+        text = [(banks[0].to(dev), None) if p is None else p for banks, p in zip(banks_v, packed)]
+        for v, (xs, _) in enumerate(views):
+            chw = torch.stack([x.to(dev) for x in xs])       # [B, 3, H, W] BGR, contiguous
+            if chw.dtype not in (torch.uint8, torch.float32):
+                chw = chw.to(torch.float32)
+            L.chw_to_hwc_u8(chw, Bf["x"][v])                 # bgr_to_rgb + NHWC, as predict
+        main = torch.cuda.current_stream()
+        if stats is not None:
+            stats.update(views=V, steps=0, trips=0, inline=False, d2h_copies=0)
+
+        def stack(res, tower, v):
+            Bf["boxes"][v].copy_(res["bboxes"], non_blocking=True)
+            Bf["scores"][v].copy_(res["scores"], non_blocking=True)
+            Bf["labels"][v].copy_(res["labels"], non_blocking=True)
+            Bf["counts"][v].copy_(res["count"], non_blocking=True)
+            Bf["flags"][v].copy_(tower.range_flags, non_blocking=True)
+
+        def merge_and_download():
+            VW.views_merge(Bf["boxes"], Bf["scores"], Bf["labels"], Bf["counts"], Bf["flip"], Bf["wh"], V, B, max_in, n_cls, iou, split_thr,
+                           max_out, Bf["out_boxes"], Bf["out_scores"], Bf["out_labels"], Bf["out_src"], Bf["out_count"], Bf["ws"])
+            Bf["pin"].copy_(Bf["stage"], non_blocking=True)  # ONE packed D2H: rows, counts, range flags
+            torch.cuda.current_stream().synchronize()
+            if stats is not None:
+                stats["d2h_copies"] += 1
+            return {k: t.clone() for k, t in Bf["host"].items()}
+
+        inline = any(t.overflowed for t in h._towers.values())       # a tower in its fp32 fallback: every step goes in line
+        host = None
+        if not inline:
+            for v, tower in enumerate(towers):
+                x = Bf["x"][v]
+                h.calibrate_first(tower, x)
+                res = tower.detect(x, text[v][0], Bf["meta"][v], overlap_post=True, text_counts=text[v][1], **kw)
+                with torch.cuda.stream(tower.post_stream):   # before the next post-process overwrites the tower's rows
+                    stack(res, tower, v)
+                    Bf["events"][v].record(tower.post_stream)
+            for v in range(V):
+                main.wait_event(Bf["events"][v])
+            host = merge_and_download()
+            if stats is not None:
+                stats["steps"] += V
+            fl = [f for (tower, row) in zip(towers, host["flags"].tolist()) if tower.precision == "fp16x3" for f in row]
+            if int(host["count"].min()) < 0 or any(fl):
+                inline = True
+                if stats is not None:
+                    stats["trips"] += 1
+        if inline:
+            torch.cuda.synchronize(dev)
+            for tower in set(towers):
+                tower.range_flags.zero_()                    # a discarded step may have raised them
+            for v, tower in enumerate(towers):
+                x, m, (bank, counts_dev) = Bf["x"][v], Bf["meta"][v], text[v]
+                run = lambda: h.detect(tower, x, bank, m, text_counts=counts_dev, **kw)
+                res = run()
+                recal = (lambda: h.recalibrate(tower, x)) if h.auto_calibrate else None
+                tower.checked_counts(res, run, recal)
+                h.precision = "fp32" if tower.overflowed else h._asked_precision
+                stack(res, tower, v)
+            Bf["flags"].zero_()
+            host = merge_and_download()
+            if stats is not None:
+                stats["steps"] += V
+                stats["inline"] = True
+            if int(host["count"].min()) < 0:
+                raise RuntimeError("non-finite scores survived the in-line range guard")
+        out = []
+        for b, s in enumerate(views[0][1]):
+            n = int(host["count"][b])
+            if s is None:
+                s = DetDataSample()
+            elif isinstance(s, dict):
+                s = DetDataSample(metainfo=_meta_of(s))
+            s.pred_instances = InstanceData(bboxes=host["boxes"][b, :n], scores=host["scores"][b, :n],
+                                            labels=host["labels"][b, :n].to(torch.int64),
+                                            views=(host["src"][b, :n] // max_in).to(torch.int64))
+            out.append(s)
+        return out
+
+    def _views_buffers(self, V: int, B: int, max_in: int, max_out: int, shapes: tuple, dev) -> dict:
+        """Device buffers of ``predict_views`` for one geometry, kept between calls: the NHWC input of every view, the stacked
+        per-view rows, ONE control block (flip codes, image sizes, per-view metadata) with its pinned twin, the merge's
+        workspace, and ONE staging blob (merged rows, counts, range flags per view) with its pinned twin."""
+        from . import views as VW
+        key = (V, B, max_in, max_out, shapes, str(dev))
+        Bf = getattr(self, "_views", None)
+        if Bf is not None and Bf["key"] == key:
+            return Bf
+        f32, i32, u8 = torch.float32, torch.int32, torch.uint8
+        e = lambda *s, dt=f32: torch.empty(*s, dtype=dt, device=dev)
+
+        def blob(parts):
+            off, lay = 0, []
+            for name, shape, dt in parts:
+                nb = int(np.prod(shape)) * 4
+                lay.append((name, shape, dt, off, nb))
+                off += (nb + 255) // 256 * 256
+            return off, lay
+        Bf = dict(key=key, x=[e(B, hh, ww, 3, dt=u8) for hh, ww in shapes], boxes=e(V, B, max_in, 4), scores=e(V, B, max_in),
+                  labels=e(V, B, max_in, dt=i32), counts=e(V, B, dt=i32), ws=e(VW.merge_workspace_bytes(V, B, max_in), dt=u8),
+                  events=[torch.cuda.Event() for _ in range(V)])
+        nb, lay = blob((("flip", (V,), i32), ("wh", (B, 2), f32), ("meta", (V, B, 8), f32)))
+        Bf["ctl"], Bf["ctl_pin"], Bf["ctl_host"] = torch.zeros(nb, dtype=u8, device=dev), torch.zeros(nb, dtype=u8).pin_memory(), {}
+        for name, shape, dt, o, n in lay:
+            Bf[name] = Bf["ctl"][o:o + n].view(dt).view(shape)
+            Bf["ctl_host"][name] = Bf["ctl_pin"][o:o + n].view(dt).view(shape)
+        nb, lay = blob((("boxes", (B, max_out, 4), f32), ("scores", (B, max_out), f32), ("labels", (B, max_out), i32),
+                        ("src", (B, max_out), i32), ("count", (B,), i32), ("flags", (V, 2), i32)))
+        Bf["stage"], Bf["pin"], Bf["host"] = torch.zeros(nb, dtype=u8, device=dev), torch.zeros(nb, dtype=u8).pin_memory(), {}
+        for name, shape, dt, o, n in lay:
+            Bf["out_" + name if name != "flags" else "flags"] = Bf["stage"][o:o + n].view(dt).view(shape)
+            Bf["host"][name] = Bf["pin"][o:o + n].view(dt).view(shape)
+        self._views = Bf
+        return Bf
+
 
 MODELS.register_module(module=YOLOWorldDetector)
 MODELS.register_module(module=MultiModalYOLOBackbone)

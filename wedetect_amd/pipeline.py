@@ -370,3 +370,6 @@ class Compose:
 
     def __repr__(self):
         return "Compose(" + ", ".join(type(t).__name__ for t in self.transforms) + ")"
+
+
+TRANSFORMS.register_module(module=Compose)      # a branch of TestTimeAug that is several transforms (resize + letter step)

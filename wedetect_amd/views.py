@@ -1,0 +1,66 @@
+"""ctypes binding of the test-time-augmentation entry points (include/wedetect_hip_views.h, csrc/views.hip): ``wd_flip_u8``
+flips a batch of [n, h, w, 3] images in one launch, ``wd_views_merge`` turns the stacked per-view rows of every image into the
+rows of that image.  Like feed.py and tile.py: a version and an export list of its own, the main ABI stays as it is."""
+from __future__ import annotations
+
+import ctypes as C
+
+from . import lib as L
+
+VIEWS_ABI_VERSION = 1
+MERGE_MAX_VIEWS = 8
+MERGE_MAX_ROWS = 4096            # n_view * max_in of one image
+MERGE_MAX_OUT = 1024
+FLIP_CODES = {None: 0, "horizontal": 1, "vertical": 2, "diagonal": 3}      # mmcv imflip directions -> WD_FLIP_*
+
+EXPORTS = ("wd_views_abi_version", "wd_flip_u8", "wd_views_merge_workspace_bytes", "wd_views_merge")
+
+
+def _bind():
+    lib = L.LIB
+    for name in EXPORTS:
+        if not hasattr(lib, name):
+            raise L.WedetectHipMissing(f"{L.LIB_PATH} does not export {name}; rebuild (python -m wedetect_amd.build)")
+    vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
+    lib.wd_views_abi_version.restype = C.c_int
+    lib.wd_flip_u8.argtypes = [vp, vp, i32, i32, i32, i32, vp]
+    lib.wd_views_merge_workspace_bytes.restype = i64
+    lib.wd_views_merge_workspace_bytes.argtypes = [i32, i32, i32]
+    lib.wd_views_merge.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp]
+    if lib.wd_views_abi_version() != VIEWS_ABI_VERSION:
+        raise L.WedetectHipMissing(f"views ABI mismatch: library {lib.wd_views_abi_version()} vs binding {VIEWS_ABI_VERSION}; rebuild")
+    return lib
+
+
+LIB = _bind()
+
+
+def merge_workspace_bytes(n_view: int, batch: int, max_in: int) -> int:
+    return int(LIB.wd_views_merge_workspace_bytes(int(n_view), int(batch), int(max_in)))
+
+
+def flip_u8(src, dst, direction) -> None:
+    """``wd_flip_u8`` on the current stream.  ``src`` / ``dst``: contiguous device uint8 [h, w, 3] or [n, h, w, 3] of one shape;
+    ``direction``: 'horizontal' / 'vertical' / 'diagonal' or the code 1 .. 3."""
+    import torch
+    code = FLIP_CODES.get(direction, direction) if isinstance(direction, (str, type(None))) else int(direction)
+    if code not in (1, 2, 3):
+        raise L.WedetectHipError(f"flip_u8: direction {direction!r} (horizontal / vertical / diagonal)")
+    for t in (src, dst):
+        if t.dtype != torch.uint8 or t.dim() not in (3, 4) or t.shape[-1] != 3 or not t.is_cuda or not t.is_contiguous():
+            raise L.WedetectHipError("flip_u8: contiguous device uint8 [n, h, w, 3] (or [h, w, 3]) tensors are required")
+    if src.shape != dst.shape:
+        raise L.WedetectHipError("flip_u8: src and dst differ in shape")
+    n = int(src.shape[0]) if src.dim() == 4 else 1
+    L.check(LIB.wd_flip_u8(src.data_ptr(), dst.data_ptr(), n, int(src.shape[-3]), int(src.shape[-2]), code, L.stream_ptr()), "wd_flip_u8")
+
+
+def views_merge(boxes, scores, labels, counts, view_flip, img_wh, n_view: int, batch: int, max_in: int, n_cls: int, iou_thr: float,
+                split_thr: int, max_out: int, out_boxes, out_scores, out_labels, out_src, out_count, workspace) -> None:
+    """``wd_views_merge`` on the current stream; ``iou_thr`` is rounded as mmcv's ``float iou_threshold`` is
+    (``lib.nms_threshold``)."""
+    L.check(LIB.wd_views_merge(boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(), counts.data_ptr(), view_flip.data_ptr(),
+                               img_wh.data_ptr(), int(n_view), int(batch), int(max_in), int(n_cls), L.nms_threshold(iou_thr, L.NMS_MMCV),
+                               int(split_thr), int(max_out), out_boxes.data_ptr(), out_scores.data_ptr(), out_labels.data_ptr(),
+                               out_src.data_ptr(), out_count.data_ptr(), workspace.data_ptr(),
+                               workspace.numel() * workspace.element_size(), L.stream_ptr()), "wd_views_merge")
