@@ -15,8 +15,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libwedetect_hip.so")
-SOURCES = ["abi.hip", "conv_gemm.hip", "similarity_grouped.hip", "split_gemm.hip", "split_gemm_pre.hip", "split_gemm_p8.hip", "split_gemm_p4.hip", "split_gemm_conv.hip", "split_gemm_conv3.hip", "split_gemm_mlp.hip", "split_gemm_mlpw.hip", "probe.hip", "stem.hip", "elementwise.hip", "preprocess.hip", "text.hip", "bricks.hip", "evaluate.hip", "det_eval.hip", "postprocess.hip", "feed.hip", "tile.hip", "views.hip"]
-PUBLIC_HEADERS = ["wedetect_hip.h", "wedetect_hip_feed.h", "wedetect_hip_tile.h", "wedetect_hip_views.h"]
+SOURCES = ["abi.hip", "conv_gemm.hip", "similarity_grouped.hip", "split_gemm.hip", "split_gemm_pre.hip", "split_gemm_p8.hip", "split_gemm_p4.hip", "split_gemm_conv.hip", "split_gemm_conv3.hip", "split_gemm_mlp.hip", "split_gemm_mlpw.hip", "probe.hip", "stem.hip", "elementwise.hip", "preprocess.hip", "text.hip", "bricks.hip", "evaluate.hip", "det_eval.hip", "postprocess.hip", "feed.hip", "tile.hip", "views.hip", "fold.hip"]
+PUBLIC_HEADERS = ["wedetect_hip.h", "wedetect_hip_feed.h", "wedetect_hip_tile.h", "wedetect_hip_views.h", "wedetect_hip_fold.h"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-inline-asm",
          "-I", os.path.join(ROOT, "include"), "-I", CSRC]

@@ -13,7 +13,9 @@ namespace {
 //   p.c2   : an fp32 copy in plain rows (ldc2; with c_batch_stride: the rows of c) next to a CSPLIT output — for consumers
 //            that read fp32 (the BottleRep "+ alpha x" residual, yolo_world_pafpn.py:602-605; round 6: the region embeddings)
 // Host-side contract: n % 8 == 0, bias / res / c / c2 16-byte aligned, ldres % 4 == 0, ldc2 % 4 == 0,
-// ldc % 8 == 0 (CSPLIT) or % 4 == 0.
+// ldc % 8 == 0 (CSPLIT) or % 4 == 0.  ONE exception: a SPECIAL fp32 row output without residual and c2 (the folded
+// similarity, wd_fold_similarity) may have any n, any ldc >= n and a 4-byte aligned c — the ragged branch below stores such a
+// piece element by element, columns < n only; the bias then holds round_up(n, 8) floats.
 // ---------------------------------------------------------------------------------------
 // b0 / b1: the bias quads of channels n .. n + 7 (zeros without a bias); r0 / r1: the residual quads (read only if p.res).
 template <int ACT, bool SPECIAL, bool CSPLIT>
@@ -73,8 +75,18 @@ __device__ __forceinline__ void epi_oct_core(const WdConvGemm& p, float unscale,
     *reinterpret_cast<u32x4*>(cp) = u32x4{h0[0], h0[1], h1[0], h1[1]};
     *reinterpret_cast<u32x4*>(cp + 16) = u32x4{l0[0], l0[1], l1[0], l1[1]};
   } else {
-    *reinterpret_cast<f32x4*>(rowp + col) = o0;
-    *reinterpret_cast<f32x4*>(rowp + col + 4) = o1;
+    // ragged fp32 rows (SPECIAL outputs only, wd_conv_pp_ok: any n / ldc, e.g. the folded similarity's [B, anchors, K] for any
+    // K): element stores, columns < n only.  Wave-uniform; the aligned case keeps its two 16-byte stores.
+    if (SPECIAL && (((p.n & 7) | (p.ldc & 3)) != 0 || (reinterpret_cast<uintptr_t>(p.c) & 15u) != 0)) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        if (col + r < p.n) rowp[col + r] = o0[r];
+        if (col + 4 + r < p.n) rowp[col + 4 + r] = o1[r];
+      }
+    } else {
+      *reinterpret_cast<f32x4*>(rowp + col) = o0;
+      *reinterpret_cast<f32x4*>(rowp + col + 4) = o1;
+    }
   }
 }
 

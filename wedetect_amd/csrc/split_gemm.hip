@@ -120,7 +120,7 @@ bool wd_p8_persist_ok(int m, int n);
 // split_gemm_conv.hip: implicit-GEMM LDS-DMA kernel for pre-split activations (any geometry, every output form)
 bool wd_conv_pp_ok(const WdConvGemm& p, int flags);
 int wd_launch_conv_pp(const WdConvGemm& p, const void* w, float unscale, int flags, hipStream_t st, int ksplits, float* ws,
-                      long long ws_floats, int variant);
+                      long long ws_floats, int variant, const float* unscale_dev = nullptr);
 // split_gemm_conv3.hip: 3 x 3 / stride 1 / pad 1, one stage per (filter row, channel chunk) shared by the row's three taps
 bool wd_conv3_ok(const WdConvGemm& p, int flags);
 const char* wd_conv3_config_name(int m, int n);
@@ -319,4 +319,21 @@ extern "C" int wd_conv_gemm_split_ws(const WdConvGemm* pp, const void* w_split, 
   if (splits < 0 || workspace_bytes < 0) return WD_ERR_BAD_ARG;
   return conv_gemm_split_impl(pp, w_split, w_unscale, flags, cfg, static_cast<float*>(workspace), workspace_bytes, splits,
                               static_cast<hipStream_t>(stream));
+}
+
+// include/wedetect_hip_fold.h: one level of the FOLDED region x text similarity — the text bank folded into the level's embedding
+// conv, [K][cin] weights on the level's pre-split c2 rows — through the implicit-GEMM LDS-DMA kernel the embedding conv itself
+// runs on.  w_unscale_dev: a device float (a power of two) that multiplies w_unscale: the fold chooses the weights' pre-split
+// scale on the device, so a new bank costs no host read and a captured graph follows an in-place refold.
+extern "C" int wd_fold_similarity(const WdConvGemm* pp, const void* w_split, float w_unscale, const float* w_unscale_dev,
+                                  void* stream) {
+  if (!pp || !w_unscale_dev) return WD_ERR_BAD_ARG;
+  const WdConvGemm& p = *pp;
+  const int rc = check_split_args(p, w_split, w_unscale);
+  if (rc != WD_OK) return rc;
+  if (p.kh != 1 || p.kw != 1 || p.stride != 1 || p.pad != 0 || p.c_batch_stride <= 0 || p.res || p.c2 || p.ln_stats || p.ln_u ||
+      p.seg_rows > 0 || p.act != WD_ACT_NONE)
+    return WD_ERR_BAD_ARG;
+  if (!wd_conv_pp_ok(p, WD_SPLIT_A)) return WD_ERR_UNSUPPORTED;
+  return wd_launch_conv_pp(p, w_split, w_unscale, WD_SPLIT_A, static_cast<hipStream_t>(stream), 1, nullptr, 0, 0, w_unscale_dev);
 }

@@ -50,7 +50,7 @@ __device__ __forceinline__ void cv_wait_groups(int groups) {
 template <int NBUF, int TN, bool CSPLIT, int ABL = 0>
 __global__ void __launch_bounds__(512, NBUF <= 3 ? 4 : 2)
 split_conv_pp_kernel(const WdConvGemm p, const unsigned char* __restrict__ wsp, const float* __restrict__ zero, int k16,
-                     float unscale, int nbn, int ksplits, float* __restrict__ ws) {
+                     float unscale, int nbn, int ksplits, float* __restrict__ ws, const float* __restrict__ unscale_dev) {
   constexpr int TM = 2, BM = CV_BM, BN = 64 * TN, ROWB = CV_ROWB, STAGE = CV_STAGE, NI = CV_NI, DIST = NBUF - 1;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -258,7 +258,9 @@ split_conv_pp_kernel(const WdConvGemm p, const unsigned char* __restrict__ wsp, 
     EpiOctWalk<0, TM, TN, WD_ACT_NONE, false, false, false>::run(pr, 1.0f, mw, nw, lane, acc, patch, ops);
     return;
   }
-  epi_oct_all<TM, TN, CSPLIT, (NBUF == 4 || TN == 1)>(p, unscale, mw, nw, lane, acc, patch);   // the 128-register forms keep their residual loads in the walk
+  // weights whose pre-split scale lives on the device (wd_fold_similarity: the folded text bank): one scalar load, exact
+  const float us = unscale_dev ? unscale * *unscale_dev : unscale;
+  epi_oct_all<TM, TN, CSPLIT, (NBUF == 4 || TN == 1)>(p, us, mw, nw, lane, acc, patch);   // the 128-register forms keep their residual loads in the walk
 }
 
 // split-K second pass: one thread per (row, 8 channels); partial sums added in split order (deterministic, and the
@@ -307,7 +309,8 @@ int launch_oct_reduce(const WdConvGemm& p, const float* ws, int splits, float un
 }
 
 template <int NBUF, int TN, bool CSPLIT, int ABL = 0>
-int launch_conv_pp(const WdConvGemm& p, const void* wsp, float unscale, hipStream_t st, int ksplits, float* ws) {
+int launch_conv_pp(const WdConvGemm& p, const void* wsp, float unscale, hipStream_t st, int ksplits, float* ws,
+                   const float* unscale_dev) {
   constexpr int BN = 64 * TN, LDS = NBUF * CV_STAGE;
   const int nbm = (p.m + CV_BM - 1) / CV_BM, nbn = (p.n + BN - 1) / BN;
   const long long nblk = (long long)nbm * nbn * ksplits;
@@ -319,7 +322,7 @@ int launch_conv_pp(const WdConvGemm& p, const void* wsp, float unscale, hipStrea
   static WdAttrOnce attr;
   if (wd_set_max_lds(attr, reinterpret_cast<const void*>(k), LDS) != WD_OK) return WD_ERR_LAUNCH;
   WD_LAUNCH_GEMM(k, dim3((unsigned)nblk), dim3(512), LDS, st, p, static_cast<const unsigned char*>(wsp), zero, k16, unscale,
-                 nbn, ksplits, ws);
+                 nbn, ksplits, ws, unscale_dev);
   return wd_launch_status();
 }
 
@@ -334,25 +337,32 @@ int wd_launch_oct_reduce(const WdConvGemm& p, const float* ws, int splits, float
 
 bool wd_conv_pp_ok(const WdConvGemm& p, int flags) {
   if (!(flags & WD_SPLIT_A)) return false;
-  if (p.cin % 16 || p.k % 16 || p.lda % 8 || p.kh * p.kw > 16 || p.n % 8) return false;
-  if (!wd_aligned16(p.a) || !wd_aligned16(p.c)) return false;
+  // ragged fp32 rows (any n, any ldc >= n, c 4-byte aligned): the element-store branch of epi_oct_core, which exists in the
+  // SPECIAL fp32 row epilogues only
+  const bool special = p.out_mode != WD_OUT_ROWS || p.c_batch_stride > 0 || p.seg_rows > 0 || p.sigmoid ||
+                       p.out_scale != 1.0f || p.out_bias != 0.0f;
+  const bool ragged_ok = special && !(flags & WD_SPLIT_C) && p.out_mode == WD_OUT_ROWS && !p.res && !p.c2;
+  if (p.cin % 16 || p.k % 16 || p.lda % 8 || p.kh * p.kw > 16 || (p.n % 8 && !ragged_ok)) return false;
+  if (!wd_aligned16(p.a) || (!wd_aligned16(p.c) && !ragged_ok)) return false;
   if (p.bias && !wd_aligned16(p.bias)) return false;
   if (p.res && (!wd_aligned16(p.res) || p.ldres % 4)) return false;
   if (p.c2 && (!(flags & WD_SPLIT_C) || !wd_aligned16(p.c2) || p.ldc2 % 4 || p.ldc2 < p.n || p.out_mode != WD_OUT_ROWS))
     return false;                                     // (c_batch_stride: c2 takes c's row mapping, split_epi_oct.h)
-  if ((flags & WD_SPLIT_C) ? (p.ldc % 8 != 0) : (p.ldc % 4 != 0)) return false;
+  if ((flags & WD_SPLIT_C) ? (p.ldc % 8 != 0) : (p.ldc % 4 != 0 && !ragged_ok)) return false;
   if (p.out_mode == WD_OUT_DECONV2X2 && (p.n % 32)) return false;
   return true;
 }
 
 // variant: 0 = production choice; 3 / 4 = ring depth forced (A/B runs)
 int wd_launch_conv_pp(const WdConvGemm& p, const void* w, float unscale, int flags, hipStream_t st, int ksplits, float* ws,
-                      long long ws_floats, int variant) {
+                      long long ws_floats, int variant, const float* unscale_dev) {
   if (!wd_conv_pp_ok(p, flags)) return WD_ERR_UNSUPPORTED;
   const bool csplit = (flags & WD_SPLIT_C) != 0;
   const bool narrow = (p.n % 128) != 0 && ((p.n + 63) / 64) * 64 < ((p.n + 127) / 128) * 128;
   const long long tiles = (long long)((p.m + CV_BM - 1) / CV_BM) * (narrow ? (p.n + 63) / 64 : (p.n + 127) / 128);
   if (ksplits < 1) ksplits = 1;
+  // the split-K second pass walks whole 8-column pieces and takes w_unscale by value only
+  if (ksplits > 1 && (p.n % 8 || p.ldc % 4 || !wd_aligned16(p.c) || unscale_dev)) return WD_ERR_UNSUPPORTED;
   if (ksplits > 1 && (!ws || (long long)ksplits * p.m * p.n > ws_floats)) return WD_ERR_WORKSPACE;
   if (ksplits > (p.k >> 4)) ksplits = p.k >> 4;
   // ring depth: launches that give a CU at most one workgroup hide the load latency with a deeper ring (4 stages,
@@ -363,19 +373,19 @@ int wd_launch_conv_pp(const WdConvGemm& p, const void* w, float unscale, int fla
 #ifdef WD_DEBUG_ABLATIONS
   if (variant >= 100 && variant < 116 && !narrow && csplit) {     // timing-only builds (scripts/conv_pp_abl.py)
     switch (variant - 100) {
-      case 1: return launch_conv_pp<4, 2, true, 1>(p, w, unscale, st, 1, ws);
-      case 2: return launch_conv_pp<4, 2, true, 2>(p, w, unscale, st, 1, ws);
-      case 3: return launch_conv_pp<4, 2, true, 3>(p, w, unscale, st, 1, ws);
-      case 4: return launch_conv_pp<4, 2, true, 4>(p, w, unscale, st, 1, ws);
-      case 7: return launch_conv_pp<4, 2, true, 7>(p, w, unscale, st, 1, ws);
-      case 8: return launch_conv_pp<4, 2, true, 8>(p, w, unscale, st, 1, ws);
-      case 11: return launch_conv_pp<4, 2, true, 11>(p, w, unscale, st, 1, ws);
-      case 15: return launch_conv_pp<4, 2, true, 15>(p, w, unscale, st, 1, ws);
+      case 1: return launch_conv_pp<4, 2, true, 1>(p, w, unscale, st, 1, ws, nullptr);
+      case 2: return launch_conv_pp<4, 2, true, 2>(p, w, unscale, st, 1, ws, nullptr);
+      case 3: return launch_conv_pp<4, 2, true, 3>(p, w, unscale, st, 1, ws, nullptr);
+      case 4: return launch_conv_pp<4, 2, true, 4>(p, w, unscale, st, 1, ws, nullptr);
+      case 7: return launch_conv_pp<4, 2, true, 7>(p, w, unscale, st, 1, ws, nullptr);
+      case 8: return launch_conv_pp<4, 2, true, 8>(p, w, unscale, st, 1, ws, nullptr);
+      case 11: return launch_conv_pp<4, 2, true, 11>(p, w, unscale, st, 1, ws, nullptr);
+      case 15: return launch_conv_pp<4, 2, true, 15>(p, w, unscale, st, 1, ws, nullptr);
       default: break;
     }
   }
 #endif
-#define WD_CPP(NB, TNN, CS) launch_conv_pp<NB, TNN, CS>(p, w, unscale, st, ksplits, ws)
+#define WD_CPP(NB, TNN, CS) launch_conv_pp<NB, TNN, CS>(p, w, unscale, st, ksplits, ws, unscale_dev)
   if (nbuf == 4) {
     if (narrow) rc = csplit ? WD_CPP(4, 1, true) : WD_CPP(4, 1, false);
     else rc = csplit ? WD_CPP(4, 2, true) : WD_CPP(4, 2, false);

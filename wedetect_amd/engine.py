@@ -18,12 +18,14 @@ import contextlib
 import copy
 import math
 import os
+import warnings
 import weakref
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
+from . import fold as FD
 from . import lib as L
 from .arch import ArchSpec, CLS_MID, EMBED_DIM, REG_MID, STRIDES, get_arch, level_sizes
 from .pack import Packed
@@ -251,6 +253,27 @@ class ImageTower:
         self._embed_split_on = False                          # the head of the step being issued writes embed_s
         self._embed_split_valid = False                       # embed_s holds the split of self.embed
         self._text_split: list = []                           # (weakref to the bank tensor, version, normalize, (split buffer, unscale))
+        # The text bank FOLDED into the embedding conv ($WEDETECT_FOLD_TEXT, default on; "0" = the path above and below as it was):
+        # the BN-contrastive logit is linear in the embedding conv's input c2, so detect() scores every anchor from c2 with
+        # [K, 256] folded weights per level (_fold_text, _similarity_folded), skips the three 256 -> 768 embedding launches and
+        # computes the embeddings of the kept rows only (_kept_rows); ``embed`` materialises on demand.  fp16x3 towers
+        # on the pre-split head with ONE shared bank; fp32 towers, per-image banks, calibrate() and head() / features() on
+        # their own are untouched.
+        self.fold_text = os.environ.get("WEDETECT_FOLD_TEXT", "1") != "0"
+        self._text_fold: list = []                            # (weakref to the bank tensor, version, normalize, fold entry)
+        self.fold_launches = 0                                # folds computed (one per new bank / version / normalize)
+        self.embed_materialised = 0                           # times ``embed`` was filled in after a folded step
+        self._per_image_seen = False                          # a per-image-bank step ran on this tower: no fold from then on (_fold_for)
+        self.fold_declined_per_image = 0                      # shared-bank steps that stayed unfolded for that reason
+        self._fold_cur: Optional[dict] = None                 # the fold the head being issued / last issued skipped its embedding convs for
+        self._embed_valid = True                              # _embed holds the embeddings of the last head
+        self._c2_ready: Optional[torch.cuda.Event] = None     # the last folded step's head has written hc[l][1]
+        self._kept_g: Optional[torch.Tensor] = None           # [3, B * max_out, 256] kept c2 rows per level / [3, B * max_out, 768] their GEMM outputs
+        self._kept_t: Optional[torch.Tensor] = None
+        self._kept_es: Optional[torch.Tensor] = None          # [3, round_up(B * max_out, 8), 768] kept embeddings as hi/lo groups (banks of SIM_SPLIT_MIN rows and more)
+        self._kept_s: Optional[torch.Tensor] = None           # [3, B * max_out, K] the unfolded similarity GEMM on the kept rows' embeddings
+        self._kept_perm: Optional[torch.Tensor] = None        # [B, max_out] int32: where wd_kept_rows_reorder took each kept row from
+        self._scores_fold: Optional[tuple] = None             # (fold entry, sigmoid) when ``scores`` holds a folded similarity
         self.overflowed = False
         self.fp16x3_trips = 0            # range-guard trips of this tower (each: one re-calibration attempt, then the fp32 fallback)
         self.fp16x3_retries = 0          # returns from the fp32 fallback to the fp16x3 kernels
@@ -310,7 +333,7 @@ class ImageTower:
         self.nl = [h * w for h, w in self.lv]
         self.ntot = sum(self.nl)
         self.off = [0, self.nl[0], self.nl[0] + self.nl[1]]
-        self.embed = f(B, self.ntot, EMBED_DIM)
+        self._embed = f(B, self.ntot, EMBED_DIM)              # read through the ``embed`` property
         self.boxes = f(B, self.ntot, 4)
         self.hc = [(f(B * n, CLS_MID), f(B * n, CLS_MID)) for n in self.nl]
         self.hr = [(f(B * n, REG_MID), f(B * n, REG_MID), f(B * n, 4 * 16)) for n in self.nl]
@@ -346,9 +369,30 @@ class ImageTower:
         self.lvl_logit_scale = [float(np.float32(self.P.s[f"head{l}.logit_scale"])) for l in range(3)]
         self._prepare_fold()
 
+    @property
+    def embed(self) -> torch.Tensor:
+        """Region embeddings [B, N, 768] of the last head.  A folded detect() step (see ``fold_text``) never writes them: the
+        first read afterwards issues the three embedding launches the head skipped, from the c2 buffers the step left
+        behind, on the CURRENT stream behind the step's head — the same launches on the same inputs, so the same bits."""
+        if not self._embed_valid:
+            self._materialise_embed()
+        return self._embed
+
+    def _materialise_embed(self) -> None:
+        if torch.cuda.is_current_stream_capturing():
+            raise L.WedetectHipError("ImageTower.embed read under stream capture after a folded step")
+        # c2 (hc[l][1]) is rewritten by the next step's head only: every head kernel is issued behind the work of the stream
+        # this read happens on (the caller's: the backbone the head waits for is issued there, or behind an event of it)
+        self._after(self._c2_ready)
+        for l in range(3):
+            self._embed_conv(l, False)
+        self._embed_valid = True
+        self.embed_materialised += 1
+
     def _alloc_post(self, k: int) -> None:
         self.max_classes = k
         self.generation += 1
+        self._kept_s = None                      # sized by max_classes (_kept_rows); captured graphs point into it: same generation rule
         self.scores = torch.empty(self.B, self.ntot, k, dtype=torch.float32, device=self.dev)
         nbytes = L.topk_workspace_bytes(self.B, self.ntot * k, self.nms_pre)
         self.topk_ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.dev)
@@ -1052,15 +1096,8 @@ class ImageTower:
                        ldc=CLS_MID, k=3, act=L.ACT_SILU, split_flags=fl, a_key=f"p{l + 3}", c_key=f"h{l}.c1")
             self._conv(c1, f"head{l}.cls1.w", f"head{l}.cls1.b", c2, hin=h, win=w, cin=CLS_MID, lda=CLS_MID, n=CLS_MID,
                        ldc=CLS_MID, k=3, act=L.ACT_SILU, split_flags=fl, a_key=f"h{l}.c1", c_key=f"h{l}.c2")
-            dst = self.embed.view(-1, EMBED_DIM)[self.off[l]:]
-            if self._embed_split_on and S:
-                # hi/lo groups for the fp16x3 similarity GEMM + the fp32 rows everybody else reads, same per-image row map
-                self._conv(c2, f"head{l}.embed.w", f"head{l}.embed.b", self.embed_s[self.off[l]:], hin=h, win=w, cin=CLS_MID,
-                           lda=CLS_MID, n=EMBED_DIM, ldc=EMBED_DIM, c_batch_stride=self.ntot, split_flags=fl, a_key=f"h{l}.c2",
-                           c_key="embed", c2=dst, ldc2=EMBED_DIM)
-            else:
-                self._conv(c2, f"head{l}.embed.w", f"head{l}.embed.b", dst, hin=h, win=w, cin=CLS_MID, lda=CLS_MID,
-                           n=EMBED_DIM, ldc=EMBED_DIM, c_batch_stride=self.ntot, split_flags=fa, a_key=f"h{l}.c2")
+            if self._fold_cur is None:          # a folded step scores from c2 and embeds the kept rows only
+                self._embed_conv(l, self._embed_split_on and S)
 
         def reg_branch():
             r1, r2, dist = self.hr[l]
@@ -1088,6 +1125,20 @@ class ImageTower:
                 cls_branch()
                 self._head_evs.append(self._mark())
 
+    def _embed_conv(self, l: int, split: bool) -> None:
+        """head{l}.embed: c2 -> the level's rows of the [B, N, 768] embeddings (post contrastive-BN), pre-split head or not."""
+        (h, w), c2 = self.lv[l], self.hc[l][1]
+        S = self._neck_split()
+        dst = self._embed.view(-1, EMBED_DIM)[self.off[l]:]
+        if split:
+            # hi/lo groups for the fp16x3 similarity GEMM + the fp32 rows everybody else reads, same per-image row map
+            self._conv(c2, f"head{l}.embed.w", f"head{l}.embed.b", self.embed_s[self.off[l]:], hin=h, win=w, cin=CLS_MID,
+                       lda=CLS_MID, n=EMBED_DIM, ldc=EMBED_DIM, c_batch_stride=self.ntot, split_flags=L.SPLIT_A | L.SPLIT_C,
+                       a_key=f"h{l}.c2", c_key="embed", c2=dst, ldc2=EMBED_DIM)
+        else:
+            self._conv(c2, f"head{l}.embed.w", f"head{l}.embed.b", dst, hin=h, win=w, cin=CLS_MID, lda=CLS_MID,
+                       n=EMBED_DIM, ldc=EMBED_DIM, c_batch_stride=self.ntot, split_flags=L.SPLIT_A if S else 0, a_key=f"h{l}.c2")
+
     def _head_join(self) -> None:
         self._after(*self._head_evs)
         self._head_evs = []
@@ -1105,32 +1156,34 @@ class ImageTower:
             return False
         return self.sim_split == "1" or num_classes >= self.SIM_SPLIT_MIN
 
-    def _begin_head(self, num_classes: Optional[int], standalone: bool = False) -> None:
+    def _begin_head(self, num_classes: Optional[int], standalone: bool = False, fold: Optional[dict] = None) -> None:
         if standalone:
             # a head() outside neck_head() (tests, diagnostics): rewind the event pool to where neck() left it, or repeated calls
             # would take fresh events forever
             self._ev_i = self._ev_after_neck
             self._head_evs = []
-        self._embed_split_on = self.want_sim_split(num_classes)
+        self._fold_cur = fold                   # detect() only: the head stops at c2
+        self._embed_valid = fold is None
+        self._embed_split_on = fold is None and self.want_sim_split(num_classes)
         if self._embed_split_on and self.embed_s is None:
             rows = (self.B * self.ntot + 7) // 8 * 8
             self.embed_s = torch.empty(rows, EMBED_DIM, dtype=torch.float32, device=self.dev)
             self.generation += 1
         self._embed_split_valid = self._embed_split_on
 
-    def head(self, num_classes: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    def head(self, num_classes: Optional[int] = None, _fold: Optional[dict] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """Region embeddings (post contrastive-BN) [B, N, 768] and decoded boxes [B, N, 4].  ``num_classes``: size of the text
         bank similarity() will be called with (selects the fp16x3 similarity path for large banks, see __init__)."""
-        self._begin_head(num_classes, standalone=True)
+        self._begin_head(num_classes, standalone=True, fold=_fold)
         for l in range(3):
             self._head_level(l)
         self._head_join()
-        self._record("embed", self.embed)       # calibrate(): the split scale of the embeddings (every level written: the whole buffer)
-        return self.embed, self.boxes
+        self._record("embed", self._embed)      # calibrate(): the split scale of the embeddings (every level written: the whole buffer)
+        return self._embed, self.boxes
 
     # ------------------------------------------------------------------ similarity
     def similarity(self, text: torch.Tensor, normalize: bool, sigmoid: bool = True,
-                   text_counts: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   text_counts: Optional[torch.Tensor] = None, _fold: Optional[dict] = None) -> torch.Tensor:
         """scores[b, n, k] = sigmoid(<embed[b,n], t_k> * exp(logit_scale_lvl) + bias_lvl).
         ``normalize``: L2-normalise the text rows first (BNContrastiveHead, yolo_world_head.py:101);
         the Uni path uses its prompt rows as stored (generate_proposal.py:1130).
@@ -1155,6 +1208,11 @@ class ImageTower:
         t = text.contiguous()
         out = self.scores.view(-1)[: self.B * self.ntot * k].view(self.B, self.ntot, k)
         seg = (self.ntot, self.off[1], self.off[2], self.lvl_scale, self.lvl_bias)
+        self._scores_fold = None
+        if _fold is not None:                     # detect(): the head stopped at c2 for this fold of ``text``
+            self._similarity_folded(_fold, out, k, sigmoid)
+            self._scores_fold = (_fold, bool(sigmoid))
+            return out
         if self._embed_split_valid and self.precision == "fp16x3" and self.want_sim_split(k):
             ts = self._split_text(t, normalize)
             if ts is not None:
@@ -1164,19 +1222,21 @@ class ImageTower:
         if normalize:
             L.l2norm_rows(t, self.text_norm[:k])
             t = self.text_norm[:k]
-        L.conv_gemm(self.embed, t, None, out, batch=1, hin=1, win=self.B * self.ntot, cin=EMBED_DIM, lda=EMBED_DIM,
+        L.conv_gemm(self._embed, t, None, out, batch=1, hin=1, win=self.B * self.ntot, cin=EMBED_DIM, lda=EMBED_DIM,
                     n=k, ldc=k, sigmoid=sigmoid, seg=seg)
         return out
 
     def _similarity_per_image(self, text: torch.Tensor, normalize: bool, sigmoid: bool,
                               text_counts: Optional[torch.Tensor]) -> torch.Tensor:
         if not isinstance(text, torch.Tensor) or text.dim() != 3 or text.dtype != torch.float32 or text.shape[2] != EMBED_DIM \
-                or not text.is_cuda or text.device != self.embed.device or text.shape[1] < 1:
+                or not text.is_cuda or text.device != self._embed.device or text.shape[1] < 1:
             raise L.WedetectHipError("per-image text banks must be one device float32 [B, k_max, 768] tensor on the tower's device")
         if text.shape[0] != self.B:
             raise L.WedetectHipError(f"per-image text banks: {text.shape[0]} banks for a tower of batch {self.B}")
+        self._per_image_seen = True
+        self._scores_fold = None
         if text_counts is not None:
-            if not isinstance(text_counts, torch.Tensor) or not text_counts.is_cuda or text_counts.device != self.embed.device:
+            if not isinstance(text_counts, torch.Tensor) or not text_counts.is_cuda or text_counts.device != self._embed.device:
                 raise L.WedetectHipError("text_counts must be a DEVICE int32 [B] tensor (the kernel reads it; the step has no host read)")
             if text_counts.dtype != torch.int32 or tuple(text_counts.shape) != (self.B,):
                 raise L.WedetectHipError(f"text_counts must be int32 of shape [{self.B}], got {text_counts.dtype} {tuple(text_counts.shape)}")
@@ -1195,7 +1255,7 @@ class ImageTower:
             t = tn.view(self.B, k, EMBED_DIM)
         out = self.scores.view(-1)[: self.B * self.ntot * k].view(self.B, self.ntot, k)
         seg = (self.ntot, self.off[1], self.off[2], self.lvl_scale, self.lvl_bias)
-        L.similarity_grouped(self.embed, t, text_counts, out, self.B, self.ntot, k, EMBED_DIM, k, seg, sigmoid=sigmoid)
+        L.similarity_grouped(self._embed, t, text_counts, out, self.B, self.ntot, k, EMBED_DIM, k, seg, sigmoid=sigmoid)
         return out
 
     def _split_text(self, t: torch.Tensor, normalize: bool):
@@ -1218,6 +1278,151 @@ class ImageTower:
         self._text_split = [e for e in self._text_split if e[0]() is not None][-1:]     # the last two live banks
         self._text_split.append((weakref.ref(t), t._version, bool(normalize), ts))
         return ts
+
+    # ------------------------------------------------------------------ text bank folded into the embedding conv
+    def _fold_for(self, text: torch.Tensor, text_counts, normalize: bool) -> Optional[dict]:
+        """The fold of ``text`` a detect() step may use, or None: fp16x3 towers on the pre-split head with ONE shared
+        device float32 [K, 768] bank, outside calibrate()."""
+        if self._per_image_seen:
+            # similarity() promises that image b of a per-image-bank step has the bits of a shared-bank step with bank b; the
+            # per-image path is the unfolded one, so a tower that has served per-image banks keeps its shared path unfolded too
+            if self.fold_text and text_counts is None and text.dim() == 2 and self.precision == "fp16x3":
+                self.fold_declined_per_image += 1
+            return None
+        if (not self.fold_text or text_counts is not None or text.dim() != 2 or self.precision != "fp16x3" or not self._neck_split()
+                or self._calib is not None or text.dtype != torch.float32 or text.shape[1] != EMBED_DIM or not text.is_cuda):
+            return None
+        if self.want_sim_split(text.shape[0]) and torch.cuda.is_current_stream_capturing():
+            # banks the unfolded step scores on the fp16x3 similarity kernel (SIM_SPLIT_MIN rows and more): the kept rows of a
+            # folded step are re-scored by that kernel (_kept_rows) with the split bank of the entry, whose unscale is a HOST
+            # number: a captured graph could not follow an in-place refold, so a captured step of such a bank stays unfolded
+            return None
+        return self._fold_text(text.contiguous(), normalize)
+
+    def _fold_text(self, t: torch.Tensor, normalize: bool) -> Optional[dict]:
+        """Per level: Wf_l = t^ W_e,l [K, 256] as fp16 hi/lo groups and bf_l = t^ b_e,l [K] (W_e / b_e as packed: the contrastive
+        BN is in them; t^ = the rows normalised first when ``normalize``).  Folded ONCE per bank, keyed like ``_split_text``:
+        the same tensor OBJECT (weak reference) at the same version counter with the same ``normalize``; the last two live banks
+        are kept.  Nothing is read on the host (the pre-split scale of Wf is chosen on the device, _fold_compute), but the
+        fold is a dozen small launches with allocations: a bank first seen under stream capture takes the unfolded path for
+        that call (None), as it does in ``_split_text``."""
+        for ref, ver, norm, ent in self._text_fold:
+            if ref() is t and ver == t._version and norm == bool(normalize):
+                return ent
+        if torch.cuda.is_current_stream_capturing():
+            return None
+        ent = self._fold_compute(t, normalize, None)
+        self._text_fold = [e for e in self._text_fold if e[0]() is not None][-1:]
+        self._text_fold.append((weakref.ref(t), t._version, bool(normalize), ent))
+        return ent
+
+    def _fold_compute(self, t: torch.Tensor, normalize: bool, ent: Optional[dict]) -> dict:
+        """Fold ``t`` into a new entry, or IN PLACE into ``ent`` (GraphedDetect: its graph holds the entry's pointers).  The
+        products are formed in float64 on the device and rounded once to fp32; the weights are then multiplied by the power
+        of two that puts max |Wf| into [2^13, 2^14) (what lib.split_weights does with a host read of the maximum) and its
+        inverse stays on the device for the kernel (wd_fold_similarity: w_unscale_dev) — no synchronisation."""
+        k = t.shape[0]
+        k8 = (k + 7) // 8 * 8
+        if ent is None:
+            nbytes = int(L.LIB.wd_split_weights_bytes(k, CLS_MID))
+            ent = dict(k=k, w=[torch.empty(nbytes, dtype=torch.uint8, device=self.dev) for _ in range(3)],
+                       b=torch.zeros(3, k8, dtype=torch.float32, device=self.dev),
+                       u=torch.empty(3, dtype=torch.float32, device=self.dev),
+                       tn=torch.empty_like(t))
+        elif ent["k"] != k:
+            raise L.WedetectHipError(f"refold in place: a bank of {k} rows into a fold of {ent['k']}")
+        # tn: the rows the unfolded similarity GEMM multiplies with (_kept_rows re-scores the kept rows with it); a buffer of
+        # the entry's own: text_norm may still be read by an unfolded step on another stream
+        src = ent["tn"]
+        if normalize:
+            L.l2norm_rows(t, src)
+        else:
+            src.copy_(t)
+        if self.want_sim_split(k):               # what _split_text gives the unfolded step (one host read per new bank, as there)
+            ent["ts"] = L.split_weights(src)
+        else:
+            ent.pop("ts", None)
+        t64 = src.double()
+        for l in range(3):
+            we = self.P[f"head{l}.embed.w"].view(EMBED_DIM, -1)
+            wf = (t64 @ we.double()).float()                         # [K, 256], one rounding
+            ent["b"][l, :k].copy_((t64 @ self.P[f"head{l}.embed.b"].double()).float())
+            _, ex = torch.frexp(wf.abs().max())                      # max |wf| = m 2^ex, m in [0.5, 1)
+            one = torch.ones((), dtype=torch.float32, device=self.dev)
+            L.split_weights_scaled(wf * torch.ldexp(one, 14 - ex), ent["w"][l])
+            ent["u"][l].copy_(torch.ldexp(one, ex - 14))
+        self.fold_launches += 1
+        return ent
+
+    def _similarity_folded(self, ent: dict, out: torch.Tensor, k: int, sigmoid: bool) -> None:
+        """scores[b, off_l + n, :] = sigmoid((<c2_l[b, n], Wf_l> + bf_l) exp(scale_l) + bias_l): one launch per level (the level
+        boundaries are not tile-aligned inside an image) on the kernel the level's embedding conv runs on, reading c2 in the
+        hi/lo form cls1 wrote.  Kernel and K order are fixed by the level (K = 256 is never split): batch-invariant."""
+        if self._nh_issue:                       # folded on the caller's stream, read here on the nh stream: tell the allocator
+            for t_ in (*ent["w"], ent["b"], ent["u"]):
+                t_.record_stream(torch.cuda.current_stream())
+        flat = out.view(-1)
+        for l in range(3):
+            sa = self.sscale.get(f"h{l}.c2", 1.0)      # c2 was multiplied by its split scale: divide it out (exact)
+            FD.fold_similarity(self.hc[l][1], ent["w"][l], 1.0 / sa, ent["u"][l:l + 1], ent["b"][l], flat[self.off[l] * k:],
+                               batch=self.B, rows=self.nl[l], cin=CLS_MID, n=k, c_batch_stride=self.ntot,
+                               out_scale=self.lvl_scale[l], out_bias=self.lvl_bias[l], sigmoid=sigmoid, range_flag=self.range_flag)
+
+    def _kept_rows(self, ent: dict, sigmoid: bool, with_embed: bool) -> None:
+        """The kept rows of a folded step, made what the unfolded step returns.  Their c2 rows are gathered by level and run
+        through the level's embedding GEMM — the instantiation the embedding conv runs on (batch-stride rows on the
+        implicit-GEMM kernel; K = 256 is never split and a row's result does not depend on its tile), so bit for bit the
+        embeddings the unfolded step gathers from the full tensor.  The folded scores differ from the unfolded ones in
+        their last bits (the fold re-associates the product), which is enough to swap near-tied neighbours in the output:
+        the unfolded similarity GEMM (wd_conv_gemm picks its kernel by the bank size alone and its row results do not depend
+        on the row count; from SIM_SPLIT_MIN rows wd_similarity_split, one kernel, on the embeddings' hi/lo groups written
+        by the embedding GEMM's dual-format epilogue, as in _embed_conv) therefore runs on the kept embeddings, per level with that level's scale and bias, and
+        wd_kept_rows_reorder gives the kept rows those scores and the order they imply.  Where the two steps keep the same
+        (image, anchor, label) triples — they can differ where the last bits of a score decide a threshold, the nms_pre cut
+        or a suppression — the outputs are identical.
+        c2 (hc[l][1]) therefore outlives the head until this has run: the buffers are the head's own, and wait_post() precedes
+        every head kernel of the next step, so nothing is double-buffered."""
+        rows, k = self.B * self.max_out, ent["k"]
+        if self._kept_g is None:
+            self._kept_g = torch.empty(3, rows, CLS_MID, dtype=torch.float32, device=self.dev)
+            self._kept_t = torch.empty(3, rows, EMBED_DIM, dtype=torch.float32, device=self.dev)
+            self._kept_perm = torch.empty(self.B, self.max_out, dtype=torch.int32, device=self.dev)
+        if self._kept_s is None:
+            # ONE allocation per max_classes (k <= max_classes: similarity() grows it through _alloc_post, which bumps
+            # ``generation`` and drops this buffer): a captured graph holds its pointer, a later step with a larger bank must
+            # not move it
+            self._kept_s = torch.empty(3 * rows * self.max_classes, dtype=torch.float32, device=self.dev)
+        if not torch.cuda.is_current_stream_capturing():
+            # folded on the caller's stream, read here on the post stream; the cache may drop the entry at the next detect()
+            # while this post-process still runs
+            for t_ in (ent["tn"], *(ent["ts"][:1] if ent.get("ts") is not None else ())):
+                t_.record_stream(torch.cuda.current_stream())
+        ks = self._kept_s[: 3 * rows * k].view(3, rows, k)
+        ts = ent.get("ts") if self.want_sim_split(k) else None
+        if ts is not None and self._kept_es is None:       # wd_similarity_split reads whole groups of 8 rows
+            self._kept_es = torch.zeros(3, (rows + 7) // 8 * 8, EMBED_DIM, dtype=torch.float32, device=self.dev)
+        FD.kept_rows_gather([c[1] for c in self.hc], self.nl, CLS_MID, self.out_anchors, self.out_count, self.max_out, self.B,
+                            self._kept_g)
+        for l in range(3):
+            # similarity()'s launch on these rows; every row is of level l: seg ends (rows, rows) / (0, rows) / (0, 0)
+            seg = (rows, rows if l == 0 else 0, rows if l < 2 else 0, self.lvl_scale, self.lvl_bias)
+            if ts is not None:
+                self._conv(self._kept_g[l], f"head{l}.embed.w", f"head{l}.embed.b", self._kept_es[l], hin=1, win=self.max_out,
+                           cin=CLS_MID, lda=CLS_MID, n=EMBED_DIM, ldc=EMBED_DIM, c_batch_stride=self.max_out,
+                           split_flags=L.SPLIT_A | L.SPLIT_C, a_key=f"h{l}.c2", c_key="embed", c2=self._kept_t[l], ldc2=EMBED_DIM)
+                L.similarity_split(self._kept_es[l], rows, ts[0], ts[1] / self.sscale.get("embed", 1.0), ks[l], k, EMBED_DIM, k,
+                                   seg=seg, sigmoid=sigmoid, range_flag=self.range_flag)
+                continue
+            self._conv(self._kept_g[l], f"head{l}.embed.w", f"head{l}.embed.b", self._kept_t[l], hin=1, win=self.max_out,
+                       cin=CLS_MID, lda=CLS_MID, n=EMBED_DIM, ldc=EMBED_DIM, c_batch_stride=self.max_out, split_flags=L.SPLIT_A,
+                       a_key=f"h{l}.c2")
+            L.conv_gemm(self._kept_t[l], ent["tn"], None, ks[l], batch=1, hin=1, win=rows, cin=EMBED_DIM, lda=EMBED_DIM,
+                        n=k, ldc=k, sigmoid=sigmoid, seg=seg)
+        FD.kept_rows_reorder(ks, k, self.ntot, self.off[1], self.off[2], self.out_boxes, self.out_scores, self.out_labels,
+                             self.out_anchors, self.out_count, self.max_out, self.B, self._kept_perm)
+        if with_embed:
+            FD.kept_rows_select(self._kept_t, EMBED_DIM, self.off[1], self.off[2], self.out_anchors, self.out_count, self.max_out,
+                                self.B, self.out_embed, self._kept_perm)
 
     # ------------------------------------------------------------------ post-process
     NMS_MODES = {"vanilla": L.NMS_VANILLA, "torchvision": L.NMS_TORCHVISION, "mmcv": L.NMS_MMCV}
@@ -1244,11 +1449,20 @@ class ImageTower:
             nms_param = {L.NMS_VANILLA: 0, L.NMS_TORCHVISION: L.TV_TRICK_MAX_NUMEL[nms_device], L.NMS_MMCV: L.MMCV_SPLIT_THR}[mode]
         L.topk_candidates(scores, B, n * k, float(np.float32(score_thr)), self.nms_pre, self.cand_idx,
                           self.cand_score, self.cand_count, self.topk_ws)
+        # a folded step's scores: no embedding tensor to gather from, and the kept rows take the unfolded scores and order
+        folded = self._scores_fold if scores.data_ptr() == self.scores.data_ptr() else None
+        if folded is not None and folded[0]["k"] != k:
+            folded = None
+        gather = with_embed and folded is None
+        if gather and not self._embed_valid:     # scores of the caller's own after a folded step: the rows come from ``embed``
+            self._materialise_embed()
         L.nms_gather(self.cand_idx, self.cand_score, self.cand_count, self.cap, self.boxes, n, k, meta,
-                     L.nms_threshold(iou_thr, mode, nms_device), self.max_out, self.embed if with_embed else None, EMBED_DIM,
+                     L.nms_threshold(iou_thr, mode, nms_device), self.max_out, self._embed if gather else None, EMBED_DIM,
                      self.out_boxes, self.out_scores, self.out_labels, self.out_anchors, self.out_count,
-                     self.out_embed if with_embed else None, B, nms_mode=mode, mode_param=int(nms_param),
+                     self.out_embed if gather else None, B, nms_mode=mode, mode_param=int(nms_param),
                      workspace=self.nms_ws)
+        if folded is not None:
+            self._kept_rows(folded[0], folded[1], with_embed)
         res = dict(bboxes=self.out_boxes, scores=self.out_scores, labels=self.out_labels, anchors=self.out_anchors,
                    count=self.out_count)
         if with_embed:
@@ -1330,22 +1544,22 @@ class ImageTower:
         return (a >= self.off[1]).to(torch.int64) + (a >= self.off[2]).to(torch.int64)
 
     # ------------------------------------------------------------------ whole steps
-    def neck_head(self, num_classes: Optional[int] = None):
+    def neck_head(self, num_classes: Optional[int] = None, _fold: Optional[dict] = None):
         """Neck and head as ONE schedule: in DAG mode a head level is issued on the side lanes the moment its pyramid map
         exists (level 0 beside downsample2 -> Rep_n3 -> downsample1 -> Rep_n4, level 1 beside Rep_n4); otherwise the serial
         chain neck(); head()."""
         if not self._dag_on():
             self.neck()
-            return self.head(num_classes)
-        self._begin_head(num_classes)
+            return self.head(num_classes, _fold)
+        self._begin_head(num_classes, fold=_fold)
         self.neck(_level_ready=self._head_level)
         self._head_join()
-        return self.embed, self.boxes
+        return self._embed, self.boxes
 
-    def features(self, images_u8: torch.Tensor, num_classes: Optional[int] = None):
+    def features(self, images_u8: torch.Tensor, num_classes: Optional[int] = None, _fold: Optional[dict] = None):
         self.wait_post()                          # a pipelined step may still be reading the buffers the head is about to write
         self.backbone(images_u8)
-        return self.neck_head(num_classes)
+        return self.neck_head(num_classes, _fold)
 
     def detect(self, images_u8, text, meta, *, normalize_text: bool, score_thr: float, iou_thr: float = 0.7,
                with_embed: bool = False, nms: Optional[str] = None, nms_param: Optional[int] = None, nms_device: str = "cpu",
@@ -1369,10 +1583,14 @@ class ImageTower:
             nms = "mmcv" if normalize_text else "torchvision"
         # the bank size the head prepares the fp16x3 similarity operands for; per-image banks run the fp32 kernel: none
         num_classes = None if (text.dim() == 3 or text_counts is not None) else text.shape[0]
+        # the bank folded into the embedding conv (None: this step runs the unfolded path); folded here, on the caller's stream,
+        # ahead of the backbone every later stream of the step waits for
+        fold = self._fold_for(text, text_counts, normalize_text)
         if not overlap_post:
             self.wait_post()                      # a pipelined step may still be reading the buffers this one is about to write
-            self.features(images_u8, num_classes=num_classes)
-            scores = self.similarity(text, normalize=normalize_text, text_counts=text_counts)
+            self.features(images_u8, num_classes=num_classes, _fold=fold)
+            scores = self.similarity(text, normalize=normalize_text, text_counts=text_counts, _fold=fold)
+            self._mark_c2(fold)
             return self.postprocess(scores, score_thr, meta, iou_thr, with_embed, nms, nms_param, nms_device)
         if self.post_stream is None:
             self.post_stream = device_streams(self.dev, "post")[0]
@@ -1408,12 +1626,13 @@ class ImageTower:
             try:
                 if self._dag_on():
                     self.wait_post()                  # head level 0 starts inside the neck: the previous post-process must be done with
-                    self.neck_head(num_classes)       # boxes / embeddings before ANY head kernel is issued (it had the whole backbone)
+                    self.neck_head(num_classes, fold) # boxes / embeddings before ANY head kernel is issued (it had the whole backbone)
                 else:
                     self.neck()
                     self.wait_post()
-                    self.head(num_classes)
-                scores = self.similarity(text, normalize=normalize_text, text_counts=text_counts)
+                    self.head(num_classes, fold)
+                scores = self.similarity(text, normalize=normalize_text, text_counts=text_counts, _fold=fold)
+                self._mark_c2(fold)
             finally:
                 self._nh_issue = False
             self._post_ready.record(nh)
@@ -1435,6 +1654,14 @@ class ImageTower:
                 self._post_done = torch.cuda.Event()
             self._post_done.record(self.post_stream)
         return res
+
+    def _mark_c2(self, fold: Optional[dict]) -> None:
+        """After a folded step's head + similarity on the current stream: what a later read of ``embed`` waits for."""
+        if fold is None or torch.cuda.is_current_stream_capturing():
+            return
+        if self._c2_ready is None:
+            self._c2_ready = torch.cuda.Event()
+        self._c2_ready.record(torch.cuda.current_stream())
 
     def _issue_pipelined_backbone(self, images_u8: torch.Tensor, main, depth: int) -> None:
         if depth == 2:
@@ -1596,6 +1823,11 @@ class GraphedDetect:
             self.out = tower.detect(self.images, self.text, self.meta, **kw)
         # the graph holds raw pointers to tower.scores / topk_ws / text_norm: it is valid for this generation only
         self.generation = tower.generation
+        # ... and to the fold of self.text the warm-up steps made (None: the captured step is the unfolded one).  The graph reads
+        # that entry's buffers: __call__ refolds INTO them when the caller's bank changes (device work only, no host read)
+        self._fold = tower._fold_cur
+        self._normalize = normalize_text
+        self._src = None                                   # (weak reference, version) of the bank self.text / the fold hold
 
     def __call__(self, images_u8: torch.Tensor, text: torch.Tensor, meta: torch.Tensor):
         if self.generation != self.tower.generation:
@@ -1604,6 +1836,11 @@ class GraphedDetect:
         self.tower.wait_post()                 # a pipelined eager step of the same tower may still be reading its buffers
         self.images.copy_(images_u8, non_blocking=True)
         self.text.copy_(text, non_blocking=True)
+        if self._fold is not None and not (self._src is not None and self._src[0]() is text and self._src[1] == text._version):
+            self.tower._fold_compute(self.text, self._normalize, self._fold)
+            self._src = (weakref.ref(text), text._version)
         self.meta.copy_(meta, non_blocking=True)
         self.graph.replay()
+        if self._fold is not None:
+            self.tower._embed_valid = False                # the replayed head stopped at c2 (a read of tower.embed materialises)
         return self.out

@@ -278,6 +278,18 @@ def split_weights(w: torch.Tensor):
     return out, 1.0 / scale
 
 
+def split_weights_scaled(w: torch.Tensor, out: torch.Tensor) -> None:
+    """fp32 weight rows [n, k], ALREADY multiplied by their power-of-two range scale, -> fp16 hi/lo groups in ``out``
+    (wd_split_weights_bytes(n, k) bytes, rows zero-padded to a multiple of 8).  No host read: for callers that choose the
+    scale on the device (engine.ImageTower._fold_compute)."""
+    _f32(w, "w")
+    n, k = w.shape
+    w = w.contiguous()
+    if out.numel() * out.element_size() < LIB.wd_split_weights_bytes(n, k):
+        raise WedetectHipError("split_weights_scaled: output buffer too small")
+    check(LIB.wd_split_weights_padded(_p(w), n, k, 1.0, _p(out), stream_ptr()), "wd_split_weights_padded")
+
+
 def p8_workspace_bytes() -> int:
     """Bytes of the park workspace of the persistent 256 x 256 fp16x3 kernel (needs a device: CU count)."""
     return int(LIB.wd_p8_workspace_bytes())
