@@ -172,6 +172,34 @@ def _run_config(arch, b, k, fixture, precision):
         assert torch.equal(t1.embed[0], embed[i]) and torch.equal(s1[0], scores[i]), f"{tag}: image {i} alone != in the batch"
         for kk in ("bboxes", "scores", "labels", "anchors", "count"):
             assert torch.equal(r1[kk][0], res[kk][i]), f"{tag}: image {i} {kk} alone != in the batch"
+    del t1
+    # ---- the measured form at the measured size: four different batches as a stream of pipelined steps (nothing forced: bb_depth,
+    # pipe_neck, bb_chains and dag at their defaults, the form bench.py times), no synchronisation between the calls, against
+    # the same batches in line with a synchronise after each — every returned tensor bit for bit, and an in-line step right
+    # behind the last pipelined one.  tests/test_gpu_hazards.py proves the ordering of the accesses it is told about; this is
+    # the empirical cross-check where kernels of different streams really run side by side.
+    kw = dict(normalize_text=True, score_thr=0.001, with_embed=True)
+    xs = [torch.roll(x, s, dims=0) for s in range(4)]
+    ref = []
+    for xb in xs:
+        r = tower.detect(xb, text, meta, **kw)
+        torch.cuda.synchronize()
+        ref.append({kk: v.clone() for kk, v in r.items()})
+    assert not torch.equal(ref[0]["scores"], ref[1]["scores"]), f"{tag}: the rolled batches must differ"
+    got = []
+    for xb in xs:
+        r = tower.detect(xb, text, meta, overlap_post=True, **kw)
+        with torch.cuda.stream(tower.post_stream):
+            got.append({kk: v.clone() for kk, v in r.items()})
+    r = tower.detect(xs[0], text, meta, **kw)
+    tower.wait_post()
+    torch.cuda.synchronize()
+    assert tower._nh_stream is not None and tower._slot1 is not None, f"{tag}: the pipelined form did not run"
+    for i, (a_, b_) in enumerate(zip(ref, got)):
+        for kk in a_:
+            assert torch.equal(a_[kk], b_[kk]), f"{tag} batch {i}: {kk} differs between the pipelined and the in-line step"
+    for kk in ref[0]:
+        assert torch.equal(ref[0][kk], r[kk]), f"{tag}: in-line step behind a pipelined one: {kk} differs"
 
 
 @pytest.mark.parametrize("precision", ["fp16x3", "fp32"])

@@ -978,7 +978,7 @@ class YOLOWorldDetector(_DeviceModule):
             B["scores"][lo:lo + b].copy_(res["scores"], non_blocking=True)
             B["labels"][lo:lo + b].copy_(res["labels"], non_blocking=True)
             B["counts"][lo:lo + b].copy_(res["count"], non_blocking=True)
-            B["flags"][i].copy_(tower.range_flags, non_blocking=True)
+            B["flags"][i].copy_(tower.step_range_flags, non_blocking=True)
 
         def merge_and_download():
             T.tile_merge(B["boxes"], B["scores"], B["labels"], B["counts"], ctl.data_ptr(), total, max_in, n_cls, float(edge_margin),
@@ -1014,7 +1014,7 @@ class YOLOWorldDetector(_DeviceModule):
         if inline:
             torch.cuda.synchronize(dev)
             for tower in set(towers):
-                tower.range_flags.zero_()                    # a discarded step may have raised them
+                tower.clear_range_flags()                    # a discarded step may have raised them
             lo = 0
             for i, ((_, b), tower) in enumerate(zip(steps, towers)):
                 x, m = tiles[lo:lo + b], meta[lo:lo + b]
@@ -1156,7 +1156,7 @@ class YOLOWorldDetector(_DeviceModule):
             Bf["scores"][v].copy_(res["scores"], non_blocking=True)
             Bf["labels"][v].copy_(res["labels"], non_blocking=True)
             Bf["counts"][v].copy_(res["count"], non_blocking=True)
-            Bf["flags"][v].copy_(tower.range_flags, non_blocking=True)
+            Bf["flags"][v].copy_(tower.step_range_flags, non_blocking=True)
 
         def merge_and_download():
             VW.views_merge(Bf["boxes"], Bf["scores"], Bf["labels"], Bf["counts"], Bf["flip"], Bf["wh"], V, B, max_in, n_cls, iou, split_thr,
@@ -1190,7 +1190,7 @@ class YOLOWorldDetector(_DeviceModule):
         if inline:
             torch.cuda.synchronize(dev)
             for tower in set(towers):
-                tower.range_flags.zero_()                    # a discarded step may have raised them
+                tower.clear_range_flags()                    # a discarded step may have raised them
             for v, tower in enumerate(towers):
                 x, m, (bank, counts_dev) = Bf["x"][v], Bf["meta"][v], text[v]
                 run = lambda: h.detect(tower, x, bank, m, text_counts=counts_dev, **kw)

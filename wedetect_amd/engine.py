@@ -72,6 +72,10 @@ def device_streams(dev: torch.device, role: str, n: int = 1) -> List[torch.cuda.
 class ImageTower:
     PRECISIONS = ("fp32", "fp16x3")
     SPLIT_K_AUTO_PIXELS = 4 * 640 * 640
+    # Pairs of range-flag words in the ring.  With three c1..c4 sets the backbone of step j waits for the neck of step j - 3,
+    # whose head waited for the post-process of step j - 4, which the post stream runs behind whatever the caller issued there
+    # after step j - 5: five pairs order every store behind the copy of the pair's previous step; eight leave a margin.
+    FLAG_RING = 8
     SPLIT_K_MID_PIXELS = 8 * 640 * 640
 
     def __init__(self, arch, packed: Packed, batch: int, height: int, width: int, device="cuda",
@@ -279,13 +283,18 @@ class ImageTower:
         self.fp16x3_retries = 0          # returns from the fp32 fallback to the fp16x3 kernels
         self._clean_fp32_steps, self._retry_after = 0, self.FALLBACK_RETRY
         # sticky range flag of the fp16x3 GEMMs (WdConvGemm.range_flag): set by a launch whose accumulators are inf / NaN
-        self.range_flags = torch.zeros(2, dtype=torch.int32, device=torch.device(device))
-        self.range_flag = self.range_flags[0:1]
+        # A RING of flag pairs ([2 kinds, FLAG_RING] words): every detect(overlap_post=True) step takes the next pair
+        # (_next_range_flags), so a caller that copies ``step_range_flags`` on the post stream right behind its step reads words
+        # that no launch of the following steps stores into — a pair comes round again only behind waits that already order
+        # the step behind that copy (FLAG_RING).  ``range_flags`` is the whole ring: sticky over every step since the last clear.
+        self._flag_ring = torch.zeros(2, self.FLAG_RING, dtype=torch.int32, device=torch.device(device))
+        self._flag_i = 0
+        self.range_flag = self._flag_ring[0, 0:1]
         # The five neck layers that read the ConvNeXt residual streams c1..c4 directly are the only GEMMs whose inputs are
         # not bounded by construction (neither LayerNorm outputs nor activations of a BN-folded conv).  They run fp16x3
         # under their OWN range flag; if it ever trips, only they are pinned to the fp32 MFMA kernel (neck_pin) and the
         # step is repeated — the rest of the tower keeps fp16x3.  $WEDETECT_NECK_GUARD=0 pins them from the start.
-        self.range_flag2 = self.range_flags[1:2]
+        self.range_flag2 = self._flag_ring[1, 0:1]
         self.neck_pin = precision != "fp16x3" or os.environ.get("WEDETECT_NECK_GUARD", "1") == "0"
         self.dev = torch.device(device)
         if height % 32 or width % 32:
@@ -1587,7 +1596,7 @@ class ImageTower:
         # ahead of the backbone every later stream of the step waits for
         fold = self._fold_for(text, text_counts, normalize_text)
         if not overlap_post:
-            self.wait_post()                      # a pipelined step may still be reading the buffers this one is about to write
+            self.wait_post(reads=True)            # a pipelined step, or the caller on the post stream, may still be reading the buffers this one is about to write
             self.features(images_u8, num_classes=num_classes, _fold=fold)
             scores = self.similarity(text, normalize=normalize_text, text_counts=text_counts, _fold=fold)
             self._mark_c2(fold)
@@ -1595,6 +1604,7 @@ class ImageTower:
         if self.post_stream is None:
             self.post_stream = device_streams(self.dev, "post")[0]
             self._post_ready = torch.cuda.Event()
+        self._next_range_flags()
         main = torch.cuda.current_stream()
         pipe = self._pipe_neck_on()
         depth = self._bb_depth() if pipe else 1
@@ -1655,6 +1665,25 @@ class ImageTower:
             self._post_done.record(self.post_stream)
         return res
 
+    @property
+    def range_flags(self) -> torch.Tensor:
+        """Every word of the flag ring, [2, FLAG_RING]: row 0 the general flag, row 1 the neck input layers' own."""
+        return self._flag_ring
+
+    @property
+    def step_range_flags(self) -> torch.Tensor:
+        """The pair [2] of the step being issued / last issued (a strided view of the ring)."""
+        return self._flag_ring[:, self._flag_i]
+
+    def _next_range_flags(self) -> None:
+        """The next pair of the flag ring for the step about to be issued (host only: the kernels take the pointers)."""
+        i = self._flag_i = (self._flag_i + 1) % self.FLAG_RING
+        self.range_flag, self.range_flag2 = self._flag_ring[0, i:i + 1], self._flag_ring[1, i:i + 1]
+
+    def clear_range_flags(self) -> None:
+        """Zeroes every pair of the flag ring on the current stream (after a trip, or after steps whose result is discarded)."""
+        self._flag_ring.zero_()
+
     def _mark_c2(self, fold: Optional[dict]) -> None:
         """After a folded step's head + similarity on the current stream: what a later read of ``embed`` waits for."""
         if fold is None or torch.cuda.is_current_stream_capturing():
@@ -1706,11 +1735,20 @@ class ImageTower:
         v.tmp, v.hid, v.ln_part, v.ln_stats, v.patches = s1["tmp"], s1["hid"], s1["ln_part"], s1["ln_stats"], s1["patches"]
         v.park = s1["park"] if self.park is not None else None
         v._park_mlp = s1["park"]
+        if self.kws is not None:
+            # latency split-K: this backbone runs beside slot 0's on another stream, so its under-filled launches add their
+            # partial sums in a workspace of the slot's own, like its other scratch buffers
+            if s1.get("kws") is None or s1["kws"].numel() < self.kws.numel():
+                s1["kws"] = torch.empty_like(self.kws)
+                s1["kws"].record_stream(s1["stream"])     # allocated on the caller's stream, used on the slot's
+            v.kws = s1["kws"]
         if v.bb_chains != "auto":
             v.bb_chains = "1"                         # forced image chains run on slot 0 only (one set of chain workspaces)
         with torch.cuda.stream(s1["stream"]):
             s1["stream"].wait_event(s1["ready"])
             v.backbone(s1["img"])
+        if v.kws is not None:
+            s1["kws"] = v.kws                         # _lane_kws grows it on demand
         return s1["stream"]
 
     def _pipe_neck_on(self) -> bool:
@@ -1719,10 +1757,18 @@ class ImageTower:
             return False
         return self.pipe_neck == "1" or self.B * self.H * self.W >= self.PIPE_NECK_MIN_PIXELS
 
-    def wait_post(self) -> None:
-        """Makes the CURRENT stream wait for the post-process of the last ``detect(overlap_post=True)`` call (no-op otherwise)."""
-        if self._post_done is not None and not torch.cuda.is_current_stream_capturing():
-            torch.cuda.current_stream().wait_event(self._post_done)
+    def wait_post(self, reads: bool = False) -> None:
+        """Makes the CURRENT stream wait for the post-process of the last ``detect(overlap_post=True)`` call (no-op otherwise).
+        ``reads``: for everything issued to the post stream so far — the caller's own reads of the returned tensors there
+        included (what an in-line step does first: its post-process overwrites them on the caller's stream, and the
+        ``_post_done`` event was recorded before the caller could issue those reads)."""
+        if self._post_done is None or torch.cuda.is_current_stream_capturing():
+            return
+        cur = torch.cuda.current_stream()
+        if reads and cur != self.post_stream:
+            cur.wait_stream(self.post_stream)
+        else:
+            cur.wait_event(self._post_done)
 
     def checked_counts(self, res: Dict[str, torch.Tensor], rerun, recalibrate=None) -> List[int]:
         """Kept-row counts of a step on the host (the one D2H sync a caller needs anyway) with the fp16x3 range guard:
@@ -1747,10 +1793,10 @@ class ImageTower:
                 self.precision = "fp16x3"
                 recalibrate()                        # calibrate(merge=True) through the caller: its fp32 pass restores self.precision
                 self.overflowed, self._clean_fp32_steps = False, 0
-                self.range_flags.zero_()
+                self.clear_range_flags()
                 self.fp16x3_retries += 1
             return counts
-        flags = self.range_flags.tolist() if self.precision == "fp16x3" else [0, 0]
+        flags = self._flag_ring.amax(dim=1).tolist() if self.precision == "fp16x3" else [0, 0]       # sticky over every step since the last clear
         if flags[1] and not self.neck_pin:
             # a residual stream left the fp16 range in one of the neck layers that read it directly: pin those five layers to
             # the fp32 kernel (as round 1 did unconditionally) and repeat; everything else stays fp16x3
@@ -1758,12 +1804,12 @@ class ImageTower:
             warnings.warn("wedetect_amd: a backbone residual stream left the fp16 range in a neck input layer; those layers now "
                           "run the fp32 MFMA kernel")
             self.neck_pin = True
-            self.range_flags.zero_()
+            self.clear_range_flags()
             return self.checked_counts(rerun(), rerun, recalibrate)
         tripped = flags[0] != 0
         if min(counts, default=0) >= 0 and not tripped:
             return counts
-        self.range_flags.zero_()
+        self.clear_range_flags()
         if self.precision == "fp16x3":
             self.fp16x3_trips += 1
         if self.precision == "fp16x3" and recalibrate is not None:     # also with all-unit scales: a later batch may need scales < 1
@@ -1833,7 +1879,7 @@ class GraphedDetect:
         if self.generation != self.tower.generation:
             raise L.WedetectHipError("stale hipGraph: the tower re-allocated its similarity / top-k buffers (a larger class "
                                      "bank arrived) after this graph was captured; capture a new one")
-        self.tower.wait_post()                 # a pipelined eager step of the same tower may still be reading its buffers
+        self.tower.wait_post(reads=True)       # a pipelined eager step of the same tower (or its caller, on the post stream) may still be reading its buffers
         self.images.copy_(images_u8, non_blocking=True)
         self.text.copy_(text, non_blocking=True)
         if self._fold is not None and not (self._src is not None and self._src[0]() is text and self._src[1] == text._version):

@@ -376,7 +376,7 @@ class TowerBackend:
             t = res[k]
             out.append((k, t, off))
             off += (t.numel() * t.element_size() + 255) // 256 * 256
-        out.append(("range_flags", tower.range_flags, off))
+        out.append(("range_flags", tower.step_range_flags, off))
         off += 256
         return out, off
 
@@ -447,7 +447,7 @@ class TowerBackend:
         c = s.ctx
         self._feed(s)
         tower = self._tower(s)
-        tower.range_flags.zero_()                        # a discarded later step may have raised them
+        tower.clear_range_flags()                        # a discarded later step may have raised them
         text, counts_dev = self.texts(c)
         x, h = s.canvas, self.h
         run = lambda: h.detect(tower, x, text, c["meta"], text_counts=counts_dev, **self.step_kw())
