@@ -56,7 +56,16 @@ def parse_args(argv=None):
     parser.add_argument("--no-overview", action="store_true", help="no letterboxed overview of the whole image beside the crops")
     parser.add_argument("--edge-margin", default=2.0, type=float,
                         help="drop rows closer than this many pixels to an interior side of their crop")
-    return parser.parse_args(argv)
+    parser.add_argument("--best-class", action="store_true",
+                        help="single-label detection: one label per box, the best name of the bank (the reference's multi_label=False)")
+    parser.add_argument("--agnostic-nms", action="store_true",
+                        help="with --best-class: NMS across labels (mmcv batched_nms class_agnostic=True)")
+    args = parser.parse_args(argv)
+    if args.agnostic_nms and not args.best_class:
+        parser.exit(2, "infer_wedetect.py: --agnostic-nms needs --best-class\n")
+    if args.best_class and args.tile > 0:
+        parser.exit(2, "infer_wedetect.py: --best-class is not implemented for tiled inference (--tile)\n")
+    return args
 
 
 def read_texts(spec: str):
@@ -122,6 +131,8 @@ def main(argv=None, tokenizer=None):
     if args.cfg_options is not None:
         cfg.merge_from_dict(args.cfg_options)
     cfg.work_dir = osp.join("./work_dirs", osp.splitext(osp.basename(args.config))[0])
+    if args.best_class:
+        cfg.merge_from_dict({"model.best_class": True, "model.agnostic_nms": bool(args.agnostic_nms)})
     model = init_detector(cfg, checkpoint=args.checkpoint, device=args.device, palette=["red"], tokenizer=tokenizer,
                           precision=args.precision)
     test_pipeline = Compose(cfg.test_pipeline)

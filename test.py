@@ -56,7 +56,15 @@ def parse_args(argv=None):
                         help="serial: one image at a time through the pipeline (default); stream: decode threads, one batched "
                              "pre-processing launch per batch, pipelined steps (YOLOWorldDetector.predict_stream)")
     parser.add_argument("--decode-workers", type=int, default=None, help="--loader stream: decode threads (default min(12, $OMP_NUM_THREADS or 8))")
+    parser.add_argument("--best-class", action="store_true",
+                        help="single-label detection: one label per box, the best name of the bank (the reference's multi_label=False)")
+    parser.add_argument("--agnostic-nms", action="store_true",
+                        help="with --best-class: NMS across labels (mmcv batched_nms class_agnostic=True)")
     args = parser.parse_args(argv)
+    if args.agnostic_nms and not args.best_class:
+        parser.exit(2, "test.py: --agnostic-nms needs --best-class\n")
+    if args.best_class and args.aug_test:
+        parser.exit(2, "test.py: --best-class is not implemented with --aug-test (the view merge ranks (anchor, class) rows)\n")
     if "LOCAL_RANK" not in os.environ:
         os.environ["LOCAL_RANK"] = str(args.local_rank)
     for flag, on in (("--show", args.show), ("--show-dir", args.show_dir)):
@@ -162,6 +170,8 @@ def main(argv=None):
     cfg = Config.fromfile(args.config)
     if args.cfg_options is not None:
         cfg.merge_from_dict(args.cfg_options)
+    if args.best_class:
+        cfg.merge_from_dict({"model.best_class": True, "model.agnostic_nms": bool(args.agnostic_nms)})
     if args.work_dir is not None:
         cfg.work_dir = args.work_dir
     elif cfg.get("work_dir", None) is None:

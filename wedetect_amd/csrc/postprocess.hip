@@ -16,6 +16,7 @@
 // the latter two with the libraries' fp32 coordinate offsets and their candidate-count branches.
 #include "bitonic.h"
 #include "common.h"
+#include "wedetect_hip_best.h"
 
 #pragma clang fp contract(off)
 
@@ -356,6 +357,7 @@ struct NmsForm { bool offset, agnostic; };
 __device__ __forceinline__ NmsForm nms_form(int mode, int param, int count) {
   NmsForm f{false, false};
   if (mode == WD_NMS_MMCV) { f.offset = true; f.agnostic = count < param; }
+  else if (mode == WD_NMS_MMCV_AGNOSTIC) f.agnostic = count < param;        // class_agnostic=True: boxes as they are
   else if (mode == WD_NMS_TORCHVISION && 4ll * count <= (long long)param) { f.offset = true; f.agnostic = true; }
   return f;
 }
@@ -371,6 +373,8 @@ __device__ __forceinline__ float ord_dec(unsigned e) {
 
 // boxes.max() (and -boxes.min(), for the cross-class reach below) over an image's candidates, on the boxes NMS sees
 // (after the mmdet-order rescale when meta says so).  bounds[b] = {enc(max), enc(-min)}, zeroed by the caller.
+// LABELED (wd_nms_gather_labeled): a candidate's flat index is its anchor.
+template <bool LABELED>
 __global__ void __launch_bounds__(256) nms_bounds_kernel(const int* __restrict__ cand_idx, const int* __restrict__ cand_count,
                                                          int cand_stride, const float* __restrict__ boxes, int n_anchor,
                                                          int k, const float* __restrict__ meta, int mode, int param,
@@ -389,7 +393,7 @@ __global__ void __launch_bounds__(256) nms_bounds_kernel(const int* __restrict__
   for (int u = 0; u < 4; ++u) {
     const int i = base + u * 256 + threadIdx.x;
     if (i < count) {
-      f32x4 box = bx[ci[i] / k];
+      f32x4 box = bx[LABELED ? ci[i] : ci[i] / k];
       if (pre) box = rescale_box(box, mt);
       mx = fmaxf(mx, fmaxf(fmaxf(box[0], box[1]), fmaxf(box[2], box[3])));
       mn = fminf(mn, fminf(fminf(box[0], box[1]), fminf(box[2], box[3])));
@@ -405,9 +409,13 @@ __global__ void __launch_bounds__(256) nms_bounds_kernel(const int* __restrict__
   }
 }
 
+// LABELED (wd_nms_gather_labeled): a candidate's flat index is its anchor, its label is anchor_labels[b, anchor], and k is the
+// number of labels.  Everything else — and every bit of the plain form — is shared.
+template <bool LABELED>
 __global__ void __launch_bounds__(64) nms_kernel(const int* __restrict__ cand_idx, const float* __restrict__ cand_score,
                                                  const int* __restrict__ cand_count, int cand_stride,
                                                  const float* __restrict__ boxes, int n_anchor, int k,
+                                                 const int* __restrict__ anchor_labels,
                                                  const float* __restrict__ meta, float iou_thr, int max_out, int mode,
                                                  int param, const unsigned* __restrict__ bounds,
                                                  float* __restrict__ out_boxes, float* __restrict__ out_scores,
@@ -451,6 +459,8 @@ __global__ void __launch_bounds__(64) nms_kernel(const int* __restrict__ cand_id
         else reach = (int)q;
       }
     }
+  } else if (form.agnostic) {
+    whole_list = true;                       // WD_NMS_MMCV_AGNOSTIC below split_thr: no offsets keep the labels apart
   }
   const int* ci = cand_idx + (size_t)b * cand_stride;
   const float* cs = cand_score + (size_t)b * cand_stride;
@@ -470,8 +480,13 @@ __global__ void __launch_bounds__(64) nms_kernel(const int* __restrict__ cand_id
     n_anchor_ = 0; n_label = -1; n_score = 0.f; n_box = f32x4{0.f, 0.f, 0.f, 0.f};
     if (i < count) {
       const int idx = ci[i];
-      n_anchor_ = idx / k;
-      n_label = idx - n_anchor_ * k;
+      if (LABELED) {
+        n_anchor_ = idx;
+        n_label = anchor_labels[(size_t)b * n_anchor + idx];
+      } else {
+        n_anchor_ = idx / k;
+        n_label = idx - n_anchor_ * k;
+      }
       n_score = cs[i];
       n_box = bx[n_anchor_];
     }
@@ -640,18 +655,22 @@ extern "C" int64_t wd_nms_workspace_bytes(int32_t batch) {
   return batch <= 0 ? 0 : (int64_t)align256((size_t)batch * 2 * sizeof(unsigned));
 }
 
-extern "C" int wd_nms_gather(const int32_t* cand_idx, const float* cand_score, const int32_t* cand_count,
+template <bool LABELED>
+static int nms_gather_impl(const int32_t* cand_idx, const float* cand_score, const int32_t* cand_count,
                              int32_t cand_stride, const float* boxes, int32_t n_anchor, int32_t k, const float* meta,
                              float iou_thr, int32_t max_out, int32_t nms_mode, int32_t mode_param, const float* embed,
                              int32_t embed_dim, float* out_boxes, float* out_scores, int32_t* out_labels,
                              int32_t* out_anchors, int32_t* out_count, float* out_embed, int32_t batch, void* workspace,
-                             int64_t workspace_bytes, void* stream) {
+                             int64_t workspace_bytes, void* stream, const int32_t* anchor_labels) {
   if (!cand_idx || !cand_score || !cand_count || !boxes || !meta || !out_boxes || !out_scores || !out_labels ||
       !out_anchors || !out_count)
     return WD_ERR_BAD_ARG;
   if (batch <= 0 || batch > 65535 || n_anchor <= 0 || k <= 0 || max_out <= 0 || max_out > NMS_MAX_OUT || cand_stride <= 0)
     return WD_ERR_BAD_ARG;
-  if (nms_mode != WD_NMS_VANILLA && nms_mode != WD_NMS_TORCHVISION && nms_mode != WD_NMS_MMCV) return WD_ERR_BAD_ARG;
+  if (nms_mode != WD_NMS_VANILLA && nms_mode != WD_NMS_TORCHVISION && nms_mode != WD_NMS_MMCV &&
+      !(LABELED && nms_mode == WD_NMS_MMCV_AGNOSTIC))
+    return WD_ERR_BAD_ARG;
+  if (LABELED && !anchor_labels) return WD_ERR_BAD_ARG;
   if (!wd_aligned16(boxes) || !wd_aligned16(out_boxes)) return WD_ERR_BAD_ARG;
   if (embed && (!out_embed || embed_dim <= 0 || (embed_dim & 3) || !wd_aligned16(embed) || !wd_aligned16(out_embed)))
     return WD_ERR_BAD_ARG;
@@ -661,14 +680,37 @@ extern "C" int wd_nms_gather(const int32_t* cand_idx, const float* cand_score, c
     if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 3u)) return WD_ERR_BAD_ARG;
     if (workspace_bytes < wd_nms_workspace_bytes(batch)) return WD_ERR_WORKSPACE;
     hipLaunchKernelGGL(fill_u32_kernel, dim3((2 * batch + 255) / 256), dim3(256), 0, st, bounds, 0u, (long long)2 * batch);
-    hipLaunchKernelGGL(nms_bounds_kernel, dim3((cand_stride + 1023) / 1024, batch), dim3(256), 0, st, cand_idx, cand_count,
+    hipLaunchKernelGGL(nms_bounds_kernel<LABELED>, dim3((cand_stride + 1023) / 1024, batch), dim3(256), 0, st, cand_idx, cand_count,
                        cand_stride, boxes, n_anchor, k, meta, nms_mode, mode_param, bounds);
   }
-  hipLaunchKernelGGL(nms_kernel, dim3(batch), dim3(64), 0, st, cand_idx, cand_score, cand_count, cand_stride, boxes,
-                     n_anchor, k, meta, iou_thr, max_out, nms_mode, mode_param, bounds, out_boxes, out_scores, out_labels,
+  hipLaunchKernelGGL(nms_kernel<LABELED>, dim3(batch), dim3(64), 0, st, cand_idx, cand_score, cand_count, cand_stride, boxes,
+                     n_anchor, k, anchor_labels, meta, iou_thr, max_out, nms_mode, mode_param, bounds, out_boxes, out_scores, out_labels,
                      out_anchors, out_count);
   if (embed)
     hipLaunchKernelGGL(gather_embed_kernel, dim3(max_out, batch), dim3(64), 0, st, embed, n_anchor, embed_dim,
                        out_anchors, out_count, max_out, out_embed);
   return wd_launch_status();
+}
+
+extern "C" int wd_nms_gather(const int32_t* cand_idx, const float* cand_score, const int32_t* cand_count,
+                             int32_t cand_stride, const float* boxes, int32_t n_anchor, int32_t k, const float* meta,
+                             float iou_thr, int32_t max_out, int32_t nms_mode, int32_t mode_param, const float* embed,
+                             int32_t embed_dim, float* out_boxes, float* out_scores, int32_t* out_labels,
+                             int32_t* out_anchors, int32_t* out_count, float* out_embed, int32_t batch, void* workspace,
+                             int64_t workspace_bytes, void* stream) {
+  return nms_gather_impl<false>(cand_idx, cand_score, cand_count, cand_stride, boxes, n_anchor, k, meta, iou_thr, max_out, nms_mode,
+                                mode_param, embed, embed_dim, out_boxes, out_scores, out_labels, out_anchors, out_count, out_embed,
+                                batch, workspace, workspace_bytes, stream, nullptr);
+}
+
+// include/wedetect_hip_best.h: one score per anchor, labels from an array; WD_NMS_MMCV_AGNOSTIC
+extern "C" int wd_nms_gather_labeled(const int32_t* cand_idx, const float* cand_score, const int32_t* cand_count, int32_t cand_stride,
+                                     const float* boxes, int32_t n_anchor, const int32_t* anchor_labels, int32_t n_label,
+                                     const float* meta, float iou_thr, int32_t max_out, int32_t nms_mode, int32_t mode_param,
+                                     const float* embed, int32_t embed_dim, float* out_boxes, float* out_scores,
+                                     int32_t* out_labels, int32_t* out_anchors, int32_t* out_count, float* out_embed,
+                                     int32_t batch, void* workspace, int64_t workspace_bytes, void* stream) {
+  return nms_gather_impl<true>(cand_idx, cand_score, cand_count, cand_stride, boxes, n_anchor, n_label, meta, iou_thr, max_out, nms_mode,
+                               mode_param, embed, embed_dim, out_boxes, out_scores, out_labels, out_anchors, out_count, out_embed,
+                               batch, workspace, workspace_bytes, stream, anchor_labels);
 }

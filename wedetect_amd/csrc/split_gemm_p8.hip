@@ -194,6 +194,11 @@ __device__ __forceinline__ void p8_retr_epilogue(const WdConvGemm& p, const P8Re
   }
 }
 
+constexpr int P8VAR_BEST = 16384;       // best class per region row (wd_best_similarity_split): p8_best_epilogue, at the end of this file
+template <int TM, int TN>
+__device__ __forceinline__ void p8_best_epilogue(const WdConvGemm& p, unsigned long long* __restrict__ key, int cls_offset, float unscale,
+                                                 int mw, int nw, int lane, const f32x16 (&acc)[TM][TN]);
+
 template <int VAR, int ABL = 0, bool PERSIST = false>
 __global__ void __launch_bounds__(512, 2)
 split_gemm_p8_kernel(const WdConvGemm p, const unsigned char* __restrict__ wsp, int k16, float unscale, int nbn,
@@ -513,6 +518,10 @@ split_gemm_p8_kernel(const WdConvGemm p, const unsigned char* __restrict__ wsp, 
       p8_retr_epilogue<TM, TN>(p, rt, unscale, m0 + group * 128, n0 + wn * 64, lane, acc);
       continue;
     }
+    if constexpr ((VAR & P8VAR_BEST) != 0) {                        // key pointer / cls_offset travel in rt.out / rt.ldo
+      p8_best_epilogue<TM, TN>(p, reinterpret_cast<unsigned long long*>(rt.out), rt.ldo, unscale, m0 + group * 128, n0 + wn * 64, lane, acc);
+      continue;
+    }
     const EpiVec ev{vec_c, vec_res, vec_bias, unscale};
     const int mw = m0 + group * 128, nw = n0 + wn * 64;
     float* patch = reinterpret_cast<float*>(smem_raw) + wave * 32 * EPI_LDT;
@@ -576,7 +585,7 @@ int p8_gang(int nbn) { return nbn % 8 == 0 ? 8 : nbn % 4 == 0 ? 4 : nbn % 2 == 0
 
 template <int VAR, int ABL = 0, bool PERSIST = false>
 int launch_p8(const WdConvGemm& p, const void* wsp, float unscale, hipStream_t st, float* ws = nullptr, long long ws_floats = 0,
-              int arows = 0, int wrows = 0) {
+              int arows = 0, int wrows = 0, const P8Retr& rt = P8Retr{}) {
   const int nbm = (p.m + 255) / 256, nbn = (p.n + 255) / 256;
   const long long nblk = (long long)nbm * nbn;
   if (nblk <= 0 || nblk > 0x7fffffffLL) return WD_ERR_BAD_ARG;
@@ -612,7 +621,7 @@ int launch_p8(const WdConvGemm& p, const void* wsp, float unscale, hipStream_t s
   static WdAttrOnce attr;
   if (wd_set_max_lds(attr, reinterpret_cast<const void*>(k), P8_LDS) != WD_OK) return WD_ERR_LAUNCH;
   WD_LAUNCH_GEMM(k, dim3((unsigned)grid), dim3(512), P8_LDS, st, p, static_cast<const unsigned char*>(wsp), k16, unscale, nbn,
-                 vec_c, vec_res, vec_bias, ngrp, nbm, ps, P8Retr{}, p8_stagger(), arows > 0 ? arows : p.m, wrows > 0 ? wrows : p.n);
+                 vec_c, vec_res, vec_bias, ngrp, nbm, ps, rt, p8_stagger(), arows > 0 ? arows : p.m, wrows > 0 ? wrows : p.n);
   return wd_launch_status();
 }
 
@@ -713,4 +722,71 @@ int wd_launch_p8_similarity(const WdConvGemm& p, const void* t_split, float unsc
   if (p.k % 32 || p.k < 32 || p.lda % 8 || !wd_aligned16(p.a) || !wd_aligned16(t_split)) return WD_ERR_UNSUPPORTED;
   if (p.res || p.c2 || p.bias || p.act != WD_ACT_NONE || p.out_mode != WD_OUT_ROWS || p.c_batch_stride > 0 || p.ln_stats) return WD_ERR_UNSUPPORTED;
   return launch_p8<0>(p, t_split, unscale, st, nullptr, 0, (p.m + 7) & ~7, (p.n + 7) & ~7);
+}
+
+namespace {
+
+// ---- best class per region row on this kernel (wd_best_similarity_split, include/wedetect_hip_best.h) -----------------------
+// The similarity launch with another epilogue; operands NOT swapped: in the accumulator layout the region row is the LANE
+// (lane & 31) and the class the REGISTER (32 j + 8 g + 4 (lane >> 5) + q in register 4 g + q of acc[i][j]), so a lane holds 32 of
+// the wave's 64 classes for each of its TM rows.  Every valid element gets the score the materialising epilogue would have stored
+// (epi_quad<WD_ACT_NONE, true>: fmaf(v, unscale, 0), fmaf(x, oscale, obias), wd_sigmoid_fast — the same expressions, so the same
+// bits), packed as  key = score bits << 32 | (0xFFFFFFFF - (cls_offset + class)):  scores are >= +0, so the unsigned order of the
+// keys is (score ascending, class descending) and a 64-bit max keeps the LOWEST class among equal scores.  31 in-register maxima, one
+// exchange with the other half-wave, then ONE 64-bit vector atomic max per (row, wave) into key[row] — max is order-independent:
+// the result does not depend on the tile order or on how the bank is cut into launches.  A row with a non-finite accumulator
+// (an fp16 half that overflowed) gets NaN score bits, which beat every score: the unpacked score is then non-finite and
+// wd_topk_candidates reports the image.  The key pointer and cls_offset travel in P8Retr.out / P8Retr.ldo.  (Defined behind its
+// use: the template is declared in front of the kernel.)
+__device__ __forceinline__ unsigned long long p8_umax64(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
+
+template <int TM, int TN>
+__device__ __forceinline__ void p8_best_epilogue(const WdConvGemm& p, unsigned long long* __restrict__ key, int cls_offset, float unscale,
+                                                 int mw, int nw, int lane, const f32x16 (&acc)[TM][TN]) {
+  if (mw >= p.m || nw >= p.n) return;                              // wave-uniform
+  const int half = lane >> 5;
+  const int c_lane = nw + 4 * half;                                // class of (j, g, q) = c_lane + 32 j + 8 g + q
+  const unsigned inv0 = 0xFFFFFFFFu - (unsigned)cls_offset - (unsigned)c_lane;
+#pragma unroll
+  for (int i = 0; i < TM; ++i) {
+    const int m = mw + 32 * i + (lane & 31);
+    const EpiRow er = epi_row<true>(p, m < p.m ? m : p.m - 1);      // rows past the end: what the padded buffer holds there is not ours to judge
+    unsigned long long best = 0ull;                                // 0 = no class seen
+    bool bad = false;
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int cq = c_lane + 32 * j + 8 * g;
+        if (cq < p.n && m < p.m) bad |= wd_any_nonfinite4(acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          float x = fmaf(acc[i][j][4 * g + q], unscale, 0.0f);     // unscale is a power of two: exact
+          x = fmaf(x, er.oscale, er.obias);
+          x = wd_sigmoid_fast(x);
+          const unsigned long long kq = ((unsigned long long)__float_as_uint(x) << 32) | (unsigned long long)(inv0 - (unsigned)(32 * j + 8 * g + q));
+          best = p8_umax64(best, cq + q < p.n ? kq : 0ull);
+        }
+      }
+    if (bad) {
+      if (p.range_flag) *p.range_flag = 1u;
+      best = (0x7FC00000ull << 32) | (unsigned long long)inv0;
+    }
+    const unsigned olo = __shfl_xor((unsigned)best, 32, 64), ohi = __shfl_xor((unsigned)(best >> 32), 32, 64);
+    best = p8_umax64(best, ((unsigned long long)ohi << 32) | olo);
+    if ((i & 1) == half && m < p.m && best != 0ull) atomicMax(key + m, best);
+  }
+}
+
+}  // namespace
+
+// wd_best_similarity_split: the launch above with the best-class epilogue (p8_best_epilogue) in place of the stores; p.c is unused.
+// The caller has checked n_cls * k16 * 4 < 2^32 (launch_p8 refuses it too: 32-bit DMA offsets from the operand base).
+int wd_launch_p8_best(const WdConvGemm& p, const void* t_split, float unscale, unsigned long long* key, int cls_offset, hipStream_t st) {
+  if (p.k % 32 || p.k < 32 || p.lda % 8 || !wd_aligned16(p.a) || !wd_aligned16(t_split) || !key || (reinterpret_cast<uintptr_t>(key) & 7u))
+    return WD_ERR_UNSUPPORTED;
+  if (p.res || p.c2 || p.bias || p.act != WD_ACT_NONE || p.out_mode != WD_OUT_ROWS || p.c_batch_stride > 0 || p.ln_stats || !p.sigmoid)
+    return WD_ERR_UNSUPPORTED;
+  return launch_p8<P8VAR_BEST>(p, t_split, unscale, st, nullptr, 0, (p.m + 7) & ~7, (p.n + 7) & ~7,
+                               P8Retr{nullptr, nullptr, nullptr, reinterpret_cast<float*>(key), 0, cls_offset});
 }

@@ -204,6 +204,9 @@ class _TowerHolder:
         step, tests/test_gpu_detector.py).  A graph belongs to one (tower, arithmetic mode, bank size, thresholds); the
         range guard's switch to fp32 therefore captures anew."""
         self.calibrate_first(tower, images_u8)
+        if kw.get("best_class"):
+            # single-label steps run eagerly on the unfolded head (engine.ImageTower.best_scores): no graph, no fold
+            return tower.detect(images_u8, text, meta, text_counts=text_counts, **kw)
         if text.dim() == 3 or text_counts is not None:
             # one bank per image ([B, k_max, 768] + device counts): always the eager step, never captured — a graph would
             # have to own a static copy of every packed bank, and a batch of per-image banks is not launch-bound
@@ -633,8 +636,13 @@ class YOLOWorldDetector(_DeviceModule):
                  text_encoder: Optional[Callable] = None, max_classes: Optional[int] = None, precision: Optional[str] = None,
                  *, mm_neck: bool = False, num_train_classes: int = 80, num_test_classes: int = 80,
                  data_preprocessor=None, backbone=None, neck=None, bbox_head=None, train_cfg=None, init_cfg=None,
-                 tokenizer=None):
+                 tokenizer=None, best_class: bool = False, agnostic_nms: bool = False):
         super().__init__()
+        # single-label detection (the reference's test_cfg.multi_label=False / nms.class_agnostic=True, asked for with keywords
+        # of this class — also ``model.best_class`` / ``model.agnostic_nms`` of a config; ``test_cfg`` keeps the reference's keys)
+        self.best_class, self.agnostic_nms = bool(best_class), bool(agnostic_nms)
+        if self.agnostic_nms and not self.best_class:
+            raise NotImplementedError("agnostic_nms=True is built for best_class=True only (one label per region)")
         self.mm_neck, self.num_train_classes, self.num_test_classes = mm_neck, num_train_classes, num_test_classes
         self.backbone: Optional[MultiModalYOLOBackbone] = None
         if backbone is not None:
@@ -660,7 +668,8 @@ class YOLOWorldDetector(_DeviceModule):
                    max_per_img=300)
         cfg.update(test_cfg or {})
         if not cfg["multi_label"]:
-            raise NotImplementedError("only multi_label=True (every shipped config) is implemented")
+            raise NotImplementedError("test_cfg.multi_label=False is not read from test_cfg (only multi_label=True, every shipped "
+                                      "config); single-label detection is the keyword best_class=True of this class")
         nms = dict(cfg["nms"])
         if nms.get("type", "nms") != "nms":
             raise NotImplementedError(f"test_cfg.nms.type={nms.get('type')!r}: only the plain greedy 'nms' is implemented")
@@ -670,7 +679,8 @@ class YOLOWorldDetector(_DeviceModule):
         # one with the larger threshold.  class_agnostic: NMS on the un-offset boxes across classes — not built.
         if nms.get("class_agnostic", False):
             raise NotImplementedError("test_cfg.nms.class_agnostic=True (mmcv.ops.batched_nms on un-offset boxes across classes) "
-                                      "is not implemented; every shipped config uses class-aware NMS")
+                                      "is not read from test_cfg; every shipped config uses class-aware NMS.  With best_class=True the "
+                                      "keyword agnostic_nms=True of this class gives that NMS")
         if set(nms) - {"type", "iou_threshold", "split_thr", "class_agnostic", "max_num", "score_threshold"}:
             raise NotImplementedError("test_cfg.nms options "
                                       f"{sorted(set(nms) - {'type', 'iou_threshold', 'split_thr', 'class_agnostic', 'max_num', 'score_threshold'})} are not implemented")
@@ -847,7 +857,7 @@ class YOLOWorldDetector(_DeviceModule):
         run = lambda: self._h.detect(tower, x, bank, meta, text_counts=counts_dev, normalize_text=True, score_thr=self.test_cfg["score_thr"],
                                      iou_thr=self.test_cfg["nms"]["iou_threshold"], with_embed=False,
                                      # mmdet _bbox_post_process -> mmcv.ops.batched_nms(bboxes, scores, labels, cfg.nms)
-                                     nms="mmcv", nms_param=int(self.test_cfg["nms"].get("split_thr", 10000)))
+                                     nms="mmcv", nms_param=int(self.test_cfg["nms"].get("split_thr", 10000)), **self._best_kw())
         res = run()
         recal = (lambda: self._h.recalibrate(tower, x)) if self._h.auto_calibrate else None
         counts = tower.checked_counts(res, run, recal)
@@ -877,6 +887,14 @@ class YOLOWorldDetector(_DeviceModule):
         return predict_stream(MmdetBackend(self, pipeline_cfg, rescale), data_infos, batch_size, decode_workers, stats)
 
     # -- tiled inference --------------------------------------------------------------------
+    def _best_kw(self) -> dict:
+        """The single-label keywords of a tower step; empty for the multi-label default (graph keys stay as they were)."""
+        return dict(best_class=True, agnostic_nms=self.agnostic_nms) if self.best_class else {}
+
+    def _refuse_best(self, what: str) -> None:
+        if self.best_class:
+            raise NotImplementedError(f"{what} with best_class=True is not implemented (the merges rank (anchor, class) candidates)")
+
     def _step_kw(self) -> dict:
         cfg = self.test_cfg
         return dict(normalize_text=True, score_thr=cfg["score_thr"], iou_thr=cfg["nms"]["iou_threshold"], with_embed=False,
@@ -905,6 +923,7 @@ class YOLOWorldDetector(_DeviceModule):
         download); the image is then run again step by step in line through ``checked_counts``, which owns the guard's logic,
         as wedetect_amd/stream.py does.  Returns a ``DetDataSample`` whose ``pred_instances`` holds HOST tensors: ``bboxes``
         (image pixels), ``scores``, ``labels`` and ``tiles`` (the plan index of the tile each row came from)."""
+        self._refuse_best("predict_tiled")
         from . import lib as L
         from . import tile as T
         from . import tiling as G
@@ -1085,6 +1104,7 @@ class YOLOWorldDetector(_DeviceModule):
         in line through ``checked_counts`` and merged again.  Returns the FIRST view's sample of every image (mmdet
         ``_merge_single_sample``); ``pred_instances`` holds HOST tensors: ``bboxes`` (original-image pixels), ``scores``,
         ``labels`` and ``views`` (the view each row came from)."""
+        self._refuse_best("predict_views")
         from . import lib as L
         from . import views as VW
         from .tta import check_tta_cfg

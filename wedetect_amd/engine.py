@@ -274,6 +274,9 @@ class ImageTower:
         self._c2_ready: Optional[torch.cuda.Event] = None     # the last folded step's head has written hc[l][1]
         self._kept_g: Optional[torch.Tensor] = None           # [3, B * max_out, 256] kept c2 rows per level / [3, B * max_out, 768] their GEMM outputs
         self._kept_t: Optional[torch.Tensor] = None
+        self._best_key: Optional[torch.Tensor] = None         # best-class keys int64 [B * N] (+ unpacked scores / labels), allocated by the first best_scores()
+        self._best_score: Optional[torch.Tensor] = None
+        self._best_label: Optional[torch.Tensor] = None
         self._kept_es: Optional[torch.Tensor] = None          # [3, round_up(B * max_out, 8), 768] kept embeddings as hi/lo groups (banks of SIM_SPLIT_MIN rows and more)
         self._kept_s: Optional[torch.Tensor] = None           # [3, B * max_out, K] the unfolded similarity GEMM on the kept rows' embeddings
         self._kept_perm: Optional[torch.Tensor] = None        # [B, max_out] int32: where wd_kept_rows_reorder took each kept row from
@@ -1478,6 +1481,103 @@ class ImageTower:
             res["embeddings"] = self.out_embed
         return res
 
+    # ------------------------------------------------------------------ best class per region (single-label detection)
+    def best_scores(self, text: torch.Tensor, normalize: bool, text_counts: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The best class of every region row of the last head as 64-bit keys (include/wedetect_hip_best.h): ``best_keys`` int64
+        [B * N], key = score bits << 32 | (0xFFFFFFFF - class), 0 = no class.  The score is the one ``similarity()`` would have
+        stored (sigmoid per element), the class the lowest that attains the maximum.  Issued where ``similarity()`` is issued,
+        behind ``wait_post()``: it clears and rewrites the keys the previous post-process reads.
+
+        One shared bank of at least SIM_SPLIT_MIN rows on an fp16x3 tower: ``wd_best_similarity_split`` — the similarity GEMM with
+        a key epilogue, class chunks of 2^20 rows; ``self.scores`` is neither used nor grown.  Everything else (smaller banks,
+        ``precision='fp32'``, the fp32 fallback, per-image banks): the similarity launch of that path into ``self.scores`` in class
+        chunks of at most 4096 columns, then ``wd_best_rows``; ``self.scores`` never exceeds B * N * 4096 floats here."""
+        from . import best as BS
+        self.wait_post()
+        rows = self.B * self.ntot
+        if self._best_key is None:
+            self._best_key = torch.empty(rows, dtype=torch.int64, device=self.dev)
+            self._best_score = torch.empty(self.B, self.ntot, dtype=torch.float32, device=self.dev)
+            self._best_label = torch.empty(self.B, self.ntot, dtype=torch.int32, device=self.dev)
+        key = self._best_key
+        key.zero_()
+        seg = (self.ntot, self.off[1], self.off[2], self.lvl_scale, self.lvl_bias)
+        self._scores_fold = None
+        if text.dim() == 3 or text_counts is not None:
+            if not isinstance(text, torch.Tensor) or text.dim() != 3:
+                raise L.WedetectHipError("per-image text banks must be one device float32 [B, k_max, 768] tensor on the tower's device")
+            k = int(text.shape[1])
+            for c0 in range(0, k, BS.ROWS_CHUNK):
+                kc = min(BS.ROWS_CHUNK, k - c0)
+                sub, cnt = text, text_counts
+                if kc != k:
+                    sub = text[:, c0:c0 + kc].contiguous()
+                    cnt = None if text_counts is None else (text_counts - c0).clamp_(0, kc).to(torch.int32)
+                out = self._similarity_per_image(sub, normalize, True, cnt)
+                BS.best_rows(out, self.B, self.ntot, kc, kc, key, c0, cnt)
+            return key
+        k = int(text.shape[0])
+        if text.dtype != torch.float32 or text.dim() != 2 or text.shape[1] != EMBED_DIM or not text.is_cuda:
+            raise L.WedetectHipError("text bank must be a device float32 [K, 768] tensor")
+        t = text.contiguous()
+        if self._embed_split_valid and self.precision == "fp16x3" and self.want_sim_split(k):
+            if k > self.text_norm.shape[0]:
+                self.text_norm = torch.empty(k, EMBED_DIM, dtype=torch.float32, device=self.dev)
+                self.generation += 1
+            ts = self._split_text(t, normalize)
+            if ts is not None:
+                unscale = ts[1] / self.sscale.get("embed", 1.0)
+                for c0 in range(0, k, BS.FUSED_CHUNK):
+                    BS.best_similarity_split(self.embed_s, rows, ts[0], unscale, min(BS.FUSED_CHUNK, k - c0), EMBED_DIM, key, c0, seg=seg,
+                                             range_flag=self.range_flag, t_row=c0)
+                return key
+        kmax = min(k, BS.ROWS_CHUNK)
+        if kmax > self.max_classes:
+            self._alloc_post(kmax)
+        if normalize:
+            if k > self.text_norm.shape[0]:
+                self.text_norm = torch.empty(k, EMBED_DIM, dtype=torch.float32, device=self.dev)
+                self.generation += 1
+            L.l2norm_rows(t, self.text_norm[:k])
+            t = self.text_norm[:k]
+        for c0 in range(0, k, BS.ROWS_CHUNK):
+            kc = min(BS.ROWS_CHUNK, k - c0)
+            out = self.scores.view(-1)[: rows * kc].view(self.B, self.ntot, kc)
+            L.conv_gemm(self._embed, t[c0:c0 + kc], None, out, batch=1, hin=1, win=rows, cin=EMBED_DIM, lda=EMBED_DIM,
+                        n=kc, ldc=kc, sigmoid=True, seg=seg)
+            BS.best_rows(out, self.B, self.ntot, kc, kc, key, c0)
+        return key
+
+    def postprocess_best(self, text: torch.Tensor, score_thr: float, meta: torch.Tensor, iou_thr: float = 0.7, with_embed: bool = True,
+                         nms: str = "vanilla", nms_param: Optional[int] = None, nms_device: str = "cpu",
+                         agnostic: bool = False) -> Dict[str, torch.Tensor]:
+        """``postprocess()`` of a ``best_scores()`` step: keys -> (score, label) per anchor -> candidates over N scores per image
+        (score desc, anchor asc, <= nms_pre) -> ``wd_nms_gather_labeled`` -> the usual result fields.  ``text`` only names the
+        number of labels.  ``agnostic``: WD_NMS_MMCV_AGNOSTIC in place of the mmcv form."""
+        from . import best as BS
+        B, n = self.B, self.ntot
+        n_label = int(text.shape[-2])
+        mode = self.NMS_MODES[nms]
+        if nms_param is None:
+            nms_param = {L.NMS_VANILLA: 0, L.NMS_TORCHVISION: L.TV_TRICK_MAX_NUMEL[nms_device], L.NMS_MMCV: L.MMCV_SPLIT_THR}[mode]
+        thr = L.nms_threshold(iou_thr, mode, nms_device)
+        if agnostic:
+            if mode != L.NMS_MMCV:
+                raise ValueError("agnostic NMS is the mmcv form's class_agnostic=True")
+            mode = BS.NMS_MMCV_AGNOSTIC
+        BS.best_unpack(self._best_key, B * n, self._best_score, self._best_label)
+        L.topk_candidates(self._best_score, B, n, float(np.float32(score_thr)), self.nms_pre, self.cand_idx, self.cand_score,
+                          self.cand_count, self.topk_ws)
+        BS.nms_gather_labeled(self.cand_idx, self.cand_score, self.cand_count, self.cap, self.boxes, n, self._best_label, n_label, meta,
+                              thr, self.max_out, self._embed if with_embed else None, EMBED_DIM, self.out_boxes, self.out_scores,
+                              self.out_labels, self.out_anchors, self.out_count, self.out_embed if with_embed else None, B,
+                              nms_mode=mode, mode_param=int(nms_param), workspace=self.nms_ws)
+        res = dict(bboxes=self.out_boxes, scores=self.out_scores, labels=self.out_labels, anchors=self.out_anchors,
+                   count=self.out_count)
+        if with_embed:
+            res["embeddings"] = self.out_embed
+        return res
+
     # ------------------------------------------------------------------ fp16x3 range calibration
     SCALE_TARGET_LOG2 = 10       # calibrate() places max |x| of every split tensor at 2^10: 2^6 of headroom below the fp16 maximum
 
@@ -1572,7 +1672,8 @@ class ImageTower:
 
     def detect(self, images_u8, text, meta, *, normalize_text: bool, score_thr: float, iou_thr: float = 0.7,
                with_embed: bool = False, nms: Optional[str] = None, nms_param: Optional[int] = None, nms_device: str = "cpu",
-               overlap_post: bool = False, text_counts: Optional[torch.Tensor] = None):
+               overlap_post: bool = False, text_counts: Optional[torch.Tensor] = None, best_class: bool = False,
+               agnostic_nms: bool = False):
         """The whole step.  ``text`` [K, 768] (one bank) or [B, k_max, 768] with ``text_counts`` (one bank per image, see
         similarity(); in line and under ``overlap_post`` alike, same bits).  ``nms`` None picks the library the reference's path of this text handling uses: normalised
         text = BNContrastiveHead of the mmdet path -> "mmcv"; prompts as stored = the Uni scripts -> "torchvision".
@@ -1587,17 +1688,32 @@ class ImageTower:
         Round 6: in this mode the neck, head and similarity GEMM of the step are issued on the tower's ``nh`` stream (``_pipe_neck_on``),
         so that they run beside the NEXT call's backbone too; ``self.x`` alternates between two c1..c4 sets.  The contract is the
         same — everything a step produces (``embed``, ``boxes``, ``scores`` included) is complete once ``wait_post()`` has been
-        honoured; a later in-line call, ``backbone()`` or ``features()`` orders itself behind the pending work by itself."""
+        honoured; a later in-line call, ``backbone()`` or ``features()`` orders itself behind the pending work by itself.
+
+        ``best_class`` (the reference's ``multi_label=False``, yolo_world_head.py:712-719): ONE label per region — the lowest class
+        that attains the row's maximum score — and the top-k ranks N candidates per image instead of N x K.  ``best_scores()``
+        stands where ``similarity()`` stands and ``postprocess_best()`` where ``postprocess()`` stands; same streams, same result
+        fields, in line and pipelined alike.  The step runs eagerly on the unfolded head.  ``agnostic_nms`` (with ``best_class``
+        and the mmcv form): ``mmcv.ops.batched_nms(..., class_agnostic=True)`` — un-offset boxes, one NMS across all labels
+        below split_thr candidates."""
         if nms is None:
             nms = "mmcv" if normalize_text else "torchvision"
+        if agnostic_nms and not best_class:
+            raise NotImplementedError("agnostic_nms=True is built for best_class=True steps only (one label per region)")
+        if agnostic_nms and nms != "mmcv":
+            raise ValueError("agnostic_nms=True is mmcv.ops.batched_nms(class_agnostic=True): nms must be 'mmcv'")
         # the bank size the head prepares the fp16x3 similarity operands for; per-image banks run the fp32 kernel: none
         num_classes = None if (text.dim() == 3 or text_counts is not None) else text.shape[0]
         # the bank folded into the embedding conv (None: this step runs the unfolded path); folded here, on the caller's stream,
         # ahead of the backbone every later stream of the step waits for
-        fold = self._fold_for(text, text_counts, normalize_text)
+        fold = None if best_class else self._fold_for(text, text_counts, normalize_text)
+        post_best = lambda: self.postprocess_best(text, score_thr, meta, iou_thr, with_embed, nms, nms_param, nms_device, agnostic_nms)
         if not overlap_post:
             self.wait_post(reads=True)            # a pipelined step, or the caller on the post stream, may still be reading the buffers this one is about to write
             self.features(images_u8, num_classes=num_classes, _fold=fold)
+            if best_class:
+                self.best_scores(text, normalize=normalize_text, text_counts=text_counts)
+                return post_best()
             scores = self.similarity(text, normalize=normalize_text, text_counts=text_counts, _fold=fold)
             self._mark_c2(fold)
             return self.postprocess(scores, score_thr, meta, iou_thr, with_embed, nms, nms_param, nms_device)
@@ -1641,7 +1757,11 @@ class ImageTower:
                     self.neck()
                     self.wait_post()
                     self.head(num_classes, fold)
-                scores = self.similarity(text, normalize=normalize_text, text_counts=text_counts, _fold=fold)
+                if best_class:
+                    scores = None
+                    self.best_scores(text, normalize=normalize_text, text_counts=text_counts)
+                else:
+                    scores = self.similarity(text, normalize=normalize_text, text_counts=text_counts, _fold=fold)
                 self._mark_c2(fold)
             finally:
                 self._nh_issue = False
@@ -1659,7 +1779,7 @@ class ImageTower:
                     t_.record_stream(nh)
         with torch.cuda.stream(self.post_stream):
             self.post_stream.wait_event(self._post_ready)
-            res = self.postprocess(scores, score_thr, meta, iou_thr, with_embed, nms, nms_param, nms_device)
+            res = post_best() if best_class else self.postprocess(scores, score_thr, meta, iou_thr, with_embed, nms, nms_param, nms_device)
             if self._post_done is None:
                 self._post_done = torch.cuda.Event()
             self._post_done.record(self.post_stream)

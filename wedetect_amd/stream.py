@@ -552,7 +552,7 @@ class MmdetBackend(TowerBackend):
     def step_kw(self):
         cfg = self.det.test_cfg
         return dict(normalize_text=True, score_thr=cfg["score_thr"], iou_thr=cfg["nms"]["iou_threshold"], with_embed=False,
-                    nms="mmcv", nms_param=int(cfg["nms"].get("split_thr", 10000)))
+                    nms="mmcv", nms_param=int(cfg["nms"].get("split_thr", 10000)), **self.det._best_kw())
 
     def result(self, c, j, host, n, tower):
         import torch
