@@ -60,7 +60,16 @@ def parse_args(argv=None):
                         help="single-label detection: one label per box, the best name of the bank (the reference's multi_label=False)")
     parser.add_argument("--agnostic-nms", action="store_true",
                         help="with --best-class: NMS across labels (mmcv batched_nms class_agnostic=True)")
+    parser.add_argument("--sparse-scores", action="store_true",
+                        help="multi-label detection without the [B, 8400, K] score tensor: candidates above the threshold as "
+                             "per-image lists (same results; a list that overflows falls back to the dense step)")
+    parser.add_argument("--sparse-cap", default=65536, type=int, help="with --sparse-scores: list entries per image, rounded up to a power of two and to at least the top-k "
+                             "capacity of test_cfg.nms_pre (32768 for 30000); up to 2^20")
     args = parser.parse_args(argv)
+    if args.sparse_scores and args.best_class:
+        parser.exit(2, "infer_wedetect.py: --sparse-scores (multi-label) and --best-class (single-label) exclude each other\n")
+    if args.sparse_scores and args.tile > 0:
+        parser.exit(2, "infer_wedetect.py: --sparse-scores is not implemented for tiled inference (--tile)\n")
     if args.agnostic_nms and not args.best_class:
         parser.exit(2, "infer_wedetect.py: --agnostic-nms needs --best-class\n")
     if args.best_class and args.tile > 0:
@@ -133,6 +142,8 @@ def main(argv=None, tokenizer=None):
     cfg.work_dir = osp.join("./work_dirs", osp.splitext(osp.basename(args.config))[0])
     if args.best_class:
         cfg.merge_from_dict({"model.best_class": True, "model.agnostic_nms": bool(args.agnostic_nms)})
+    if args.sparse_scores:
+        cfg.merge_from_dict({"model.sparse_scores": True, "model.sparse_cap": int(args.sparse_cap)})
     model = init_detector(cfg, checkpoint=args.checkpoint, device=args.device, palette=["red"], tokenizer=tokenizer,
                           precision=args.precision)
     test_pipeline = Compose(cfg.test_pipeline)

@@ -122,7 +122,7 @@ struct P8Retr {
   const float* bias;     // [region rows]
   const int* count;      // [images]: valid rows of an image (the first count[i] of its rows_per_img)
   float* out;            // [images][ldo] zero-filled: max over an image's valid rows of sigmoid(<e, t> exp(scale) + bias)
-  int rows_per_img, ldo;
+  int rows_per_img, ldo, n_cls_total, list_cap; float thr;   // n_cls_total / list_cap / thr: sparse candidates (P8VAR_SPARSE) only
 };
 
 template <int TM, int TN>
@@ -199,6 +199,8 @@ template <int TM, int TN>
 __device__ __forceinline__ void p8_best_epilogue(const WdConvGemm& p, unsigned long long* __restrict__ key, int cls_offset, float unscale,
                                                  int mw, int nw, int lane, const f32x16 (&acc)[TM][TN]);
 
+constexpr int P8VAR_SPARSE = 32768;     // candidates above a threshold (wd_sparse_similarity_split): p8_sparse_epilogue, at the end of this file
+template <int TM, int TN> __device__ __forceinline__ void p8_sparse_epilogue(const WdConvGemm& p, const P8Retr& rt, float unscale, int mw, int nw, int lane, const f32x16 (&acc)[TM][TN]);
 template <int VAR, int ABL = 0, bool PERSIST = false>
 __global__ void __launch_bounds__(512, 2)
 split_gemm_p8_kernel(const WdConvGemm p, const unsigned char* __restrict__ wsp, int k16, float unscale, int nbn,
@@ -522,6 +524,7 @@ split_gemm_p8_kernel(const WdConvGemm p, const unsigned char* __restrict__ wsp, 
       p8_best_epilogue<TM, TN>(p, reinterpret_cast<unsigned long long*>(rt.out), rt.ldo, unscale, m0 + group * 128, n0 + wn * 64, lane, acc);
       continue;
     }
+    if constexpr ((VAR & P8VAR_SPARSE) != 0) { p8_sparse_epilogue<TM, TN>(p, rt, unscale, m0 + group * 128, n0 + wn * 64, lane, acc); continue; }   // list / state / cls_offset travel in rt.out / rt.count / rt.ldo
     const EpiVec ev{vec_c, vec_res, vec_bias, unscale};
     const int mw = m0 + group * 128, nw = n0 + wn * 64;
     float* patch = reinterpret_cast<float*>(smem_raw) + wave * 32 * EPI_LDT;
@@ -789,4 +792,108 @@ int wd_launch_p8_best(const WdConvGemm& p, const void* t_split, float unscale, u
     return WD_ERR_UNSUPPORTED;
   return launch_p8<P8VAR_BEST>(p, t_split, unscale, st, nullptr, 0, (p.m + 7) & ~7, (p.n + 7) & ~7,
                                P8Retr{nullptr, nullptr, nullptr, reinterpret_cast<float*>(key), 0, cls_offset});
+}
+
+namespace {
+
+// ---- candidates above a threshold on this kernel (wd_sparse_similarity_split, include/wedetect_hip_sparse.h) ----------------
+// The layout of p8_best_epilogue: the region row is the LANE (lane & 31), the class the REGISTER, both half-waves hold the same 32
+// rows of tile i and 32 classes each.  Every valid element gets the score the materialising epilogue would have stored (the same
+// three expressions, so the same bits); the 32 scores of (lane, i) replace their accumulators (every index is a compile-time
+// constant: the loops are unrolled, nothing is indexed dynamically) and a 32-bit mask records which of them pass score > thr.
+// Slots: the lanes' popcounts become offsets by an inclusive wave prefix sum (six shuffles); where the wave's 32 rows lie inside ONE
+// image, lane 0 draws the wave's total from state[b][0] with one vector atomic and broadcasts the base — one atomic per
+// (wave, group) however many elements pass.  A group that straddles two images (rows_per_img = 8400 is no multiple of 32) lets
+// every lane with candidates draw its own.  A wave without candidates issues no atomic and skips the stores.  Keys
+// (~score bits << 32 | flat index) go out as plain 8-byte vector stores to list[b][slot] while slot < list_cap; the counter runs
+// on past the cap, which is how wd_sparse_select sees an overflow.
+template <int TM, int TN>
+__device__ __forceinline__ void p8_sparse_epilogue(const WdConvGemm& p, const P8Retr& rt, float unscale, int mw, int nw, int lane,
+                                                   const f32x16 (&acc)[TM][TN]) {
+  static_assert(TN * 16 == 32, "one 32-bit pass mask per (lane, row tile)");
+  if (mw >= p.m || nw >= p.n) return;                              // wave-uniform
+  unsigned long long* __restrict__ list = reinterpret_cast<unsigned long long*>(rt.out);
+  int* __restrict__ state = const_cast<int*>(rt.count);
+  const int rpi = rt.rows_per_img;
+  const unsigned cap = (unsigned)rt.list_cap;
+  const float thr = rt.thr;
+  const int half = lane >> 5;
+  const int c_lane = nw + 4 * half;                                // class of (j, g, q) = c_lane + 32 j + 8 g + q
+#pragma unroll
+  for (int i = 0; i < TM; ++i) {
+    const int m_first = mw + 32 * i;
+    if (m_first >= p.m) break;                                     // wave-uniform
+    const int m_last = m_first + 31 < p.m ? m_first + 31 : p.m - 1;
+    const int b_first = m_first / rpi;
+    const bool one_image = m_last / rpi == b_first;                // wave-uniform
+    const int m = m_first + (lane & 31);
+    const bool row_ok = m < p.m;
+    const int mc = row_ok ? m : p.m - 1;                           // rows past the end: what the padded buffer holds there is not ours to judge
+    const EpiRow er = epi_row<true>(p, mc);
+    const int b = one_image ? b_first : mc / rpi;
+    const unsigned flat0 = (unsigned)(mc - b * rpi) * (unsigned)rt.n_cls_total + (unsigned)rt.ldo + (unsigned)c_lane;
+    float sc[TN * 16];
+    unsigned mask = 0u;
+    bool bad = false;
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int cq = c_lane + 32 * j + 8 * g;
+        if (cq < p.n && row_ok) bad |= wd_any_nonfinite4(acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          float x = fmaf(acc[i][j][4 * g + q], unscale, 0.0f);     // unscale is a power of two: exact
+          x = fmaf(x, er.oscale, er.obias);
+          x = wd_sigmoid_fast(x);
+          sc[16 * j + 4 * g + q] = x;
+          mask |= (row_ok && cq + q < p.n && x > thr) ? (1u << (16 * j + 4 * g + q)) : 0u;
+        }
+      }
+    if (bad) {
+      if (p.range_flag) *p.range_flag = 1u;
+      state[2 * b + 1] = 1;                                        // sticky, benign race
+    }
+    const unsigned cnt = (unsigned)__popc(mask);
+    if (__ballot(cnt != 0u) == 0ull) continue;                     // wave-uniform: nothing passes in this group
+    unsigned pos;
+    if (one_image) {
+      unsigned incl = cnt;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const unsigned up = __shfl_up(incl, o, 64);
+        incl += lane >= o ? up : 0u;
+      }
+      const unsigned total = __shfl(incl, 63, 64);
+      unsigned base = 0u;
+      if (lane == 0) base = (unsigned)atomicAdd(state + 2 * b_first, (int)total);
+      base = __shfl(base, 0, 64);
+      pos = base + incl - cnt;
+    } else {
+      pos = cnt ? (unsigned)atomicAdd(state + 2 * b, (int)cnt) : 0u;
+    }
+    unsigned long long* __restrict__ lb = list + (size_t)b * cap;
+#pragma unroll
+    for (int e = 0; e < TN * 16; ++e) {
+      if ((mask >> e) & 1u) {
+        const unsigned flat = flat0 + (unsigned)(32 * (e >> 4) + 8 * ((e >> 2) & 3) + (e & 3));
+        if (pos < cap) lb[pos] = ((unsigned long long)(~__float_as_uint(sc[e])) << 32) | (unsigned long long)flat;
+        ++pos;
+      }
+    }
+  }
+}
+
+}  // namespace
+
+// wd_sparse_similarity_split: the similarity launch with the candidate epilogue (p8_sparse_epilogue) in place of the stores; p.c is
+// unused.  The caller has checked the sizes (csrc/sparse.hip).
+int wd_launch_p8_sparse(const WdConvGemm& p, const void* t_split, float unscale, unsigned long long* list, int list_cap, int* state,
+                        int rows_per_img, int n_cls_total, int cls_offset, float thr, hipStream_t st) {
+  if (p.k % 32 || p.k < 32 || p.lda % 8 || !wd_aligned16(p.a) || !wd_aligned16(t_split) || !list || !state) return WD_ERR_UNSUPPORTED;
+  if (p.res || p.c2 || p.bias || p.act != WD_ACT_NONE || p.out_mode != WD_OUT_ROWS || p.c_batch_stride > 0 || p.ln_stats || !p.sigmoid)
+    return WD_ERR_UNSUPPORTED;
+  return launch_p8<P8VAR_SPARSE>(p, t_split, unscale, st, nullptr, 0, (p.m + 7) & ~7, (p.n + 7) & ~7,
+                                 P8Retr{nullptr, nullptr, state, reinterpret_cast<float*>(list), rows_per_img, cls_offset, n_cls_total,
+                                        list_cap, thr});
 }

@@ -204,8 +204,9 @@ class _TowerHolder:
         step, tests/test_gpu_detector.py).  A graph belongs to one (tower, arithmetic mode, bank size, thresholds); the
         range guard's switch to fp32 therefore captures anew."""
         self.calibrate_first(tower, images_u8)
-        if kw.get("best_class"):
-            # single-label steps run eagerly on the unfolded head (engine.ImageTower.best_scores): no graph, no fold
+        if kw.get("best_class") or kw.get("sparse_scores"):
+            # single-label and sparse-score steps run eagerly on the unfolded head (engine.ImageTower.best_scores /
+            # sparse_candidates): no graph, no fold
             return tower.detect(images_u8, text, meta, text_counts=text_counts, **kw)
         if text.dim() == 3 or text_counts is not None:
             # one bank per image ([B, k_max, 768] + device counts): always the eager step, never captured — a graph would
@@ -636,8 +637,16 @@ class YOLOWorldDetector(_DeviceModule):
                  text_encoder: Optional[Callable] = None, max_classes: Optional[int] = None, precision: Optional[str] = None,
                  *, mm_neck: bool = False, num_train_classes: int = 80, num_test_classes: int = 80,
                  data_preprocessor=None, backbone=None, neck=None, bbox_head=None, train_cfg=None, init_cfg=None,
-                 tokenizer=None, best_class: bool = False, agnostic_nms: bool = False):
+                 tokenizer=None, best_class: bool = False, agnostic_nms: bool = False, sparse_scores: bool = False,
+                 sparse_cap: int = 65536):
         super().__init__()
+        # sparse scores (also ``model.sparse_scores`` / ``model.sparse_cap`` of a config): the multi-label step whose similarity
+        # launch writes candidate lists of ``sparse_cap`` keys per image instead of the [B, N, K] scores (engine.ImageTower.detect)
+        self.sparse_scores, self.sparse_cap = bool(sparse_scores), int(sparse_cap)
+        if self.sparse_scores and best_class:
+            raise ValueError("sparse_scores=True is the multi-label step and best_class=True the single-label one: choose one")
+        if self.sparse_scores and not 1 <= self.sparse_cap <= 1 << 20:
+            raise ValueError("sparse_cap must lie in 1 .. 2^20 keys per image")
         # single-label detection (the reference's test_cfg.multi_label=False / nms.class_agnostic=True, asked for with keywords
         # of this class — also ``model.best_class`` / ``model.agnostic_nms`` of a config; ``test_cfg`` keeps the reference's keys)
         self.best_class, self.agnostic_nms = bool(best_class), bool(agnostic_nms)
@@ -857,7 +866,8 @@ class YOLOWorldDetector(_DeviceModule):
         run = lambda: self._h.detect(tower, x, bank, meta, text_counts=counts_dev, normalize_text=True, score_thr=self.test_cfg["score_thr"],
                                      iou_thr=self.test_cfg["nms"]["iou_threshold"], with_embed=False,
                                      # mmdet _bbox_post_process -> mmcv.ops.batched_nms(bboxes, scores, labels, cfg.nms)
-                                     nms="mmcv", nms_param=int(self.test_cfg["nms"].get("split_thr", 10000)), **self._best_kw())
+                                     nms="mmcv", nms_param=int(self.test_cfg["nms"].get("split_thr", 10000)), **self._best_kw(),
+                                     **self._sparse_kw())
         res = run()
         recal = (lambda: self._h.recalibrate(tower, x)) if self._h.auto_calibrate else None
         counts = tower.checked_counts(res, run, recal)
@@ -883,6 +893,7 @@ class YOLOWorldDetector(_DeviceModule):
         replaced by ONE batched launch sequence per batch.  Yields one ``DetDataSample`` per image, in input order, each
         exactly once; ``pred_instances`` holds what ``predict`` fills, as HOST tensors.  ``stats``: a dict that receives
         the stream's counters when it ends."""
+        self._refuse_sparse("predict_stream")
         from .stream import MmdetBackend, predict_stream
         return predict_stream(MmdetBackend(self, pipeline_cfg, rescale), data_infos, batch_size, decode_workers, stats)
 
@@ -894,6 +905,16 @@ class YOLOWorldDetector(_DeviceModule):
     def _refuse_best(self, what: str) -> None:
         if self.best_class:
             raise NotImplementedError(f"{what} with best_class=True is not implemented (the merges rank (anchor, class) candidates)")
+        self._refuse_sparse(what)
+
+    def _sparse_kw(self) -> dict:
+        """The sparse-score keywords of a tower step; empty for the default (graph keys stay as they were)."""
+        return dict(sparse_scores=True, sparse_cap=self.sparse_cap) if self.sparse_scores else {}
+
+    def _refuse_sparse(self, what: str) -> None:
+        if self.sparse_scores:
+            raise NotImplementedError(f"{what} with sparse_scores=True is not implemented (its packed result blobs do not carry "
+                                      "the sparse status; use predict)")
 
     def _step_kw(self) -> dict:
         cfg = self.test_cfg

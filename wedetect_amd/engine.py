@@ -277,6 +277,20 @@ class ImageTower:
         self._best_key: Optional[torch.Tensor] = None         # best-class keys int64 [B * N] (+ unpacked scores / labels), allocated by the first best_scores()
         self._best_score: Optional[torch.Tensor] = None
         self._best_label: Optional[torch.Tensor] = None
+        # sparse scores (detect(sparse_scores=True), include/wedetect_hip_sparse.h): per-image candidate lists int64 [B, cap],
+        # counters int32 [B, 2] and select status int32 [B], allocated by the first sparse_candidates()
+        self._sparse_list: Optional[torch.Tensor] = None
+        self._sparse_state: Optional[torch.Tensor] = None
+        self._sparse_status: Optional[torch.Tensor] = None
+        self._sparse_seen: Optional[torch.Tensor] = None      # int32 [B]: the counters as the post-process saw them (a returned tensor)
+        self.sparse_overflows = 0                             # steps in which an image's list overflowed (re-run densely)
+        self.sparse_declined = 0                              # sparse steps run densely because this (bank, threshold) kept overflowing
+        self._sparse_key: Optional[tuple] = None              # (bank identity, threshold) of the last sparse request
+        self._sparse_streak = 0                               # consecutive overflowed steps of that key
+        self._sparse_off = False                              # the key overflowed twice in a row: sparse is not tried for it again
+        self._sparse_dense_once = False                       # checked_counts() is re-running an overflowed step densely
+        self._sparse_step_counted = False                     # this checked_counts() call has counted its overflow
+        self._cc_depth = 0                                    # checked_counts() recursion depth (its re-runs come back through it)
         self._kept_es: Optional[torch.Tensor] = None          # [3, round_up(B * max_out, 8), 768] kept embeddings as hi/lo groups (banks of SIM_SPLIT_MIN rows and more)
         self._kept_s: Optional[torch.Tensor] = None           # [3, B * max_out, K] the unfolded similarity GEMM on the kept rows' embeddings
         self._kept_perm: Optional[torch.Tensor] = None        # [B, max_out] int32: where wd_kept_rows_reorder took each kept row from
@@ -1578,6 +1592,126 @@ class ImageTower:
             res["embeddings"] = self.out_embed
         return res
 
+    # ------------------------------------------------------------------ sparse scores (multi-label without the score tensor)
+    def sparse_candidates(self, text: torch.Tensor, normalize: bool, score_thr: float, text_counts: Optional[torch.Tensor] = None,
+                          sparse_cap: int = 65536) -> torch.Tensor:
+        """The (anchor, class) pairs of the last head with ``score > score_thr`` as per-image lists of 64-bit keys
+        (include/wedetect_hip_sparse.h): key = ~score bits << 32 | (anchor * K + class), the key ``wd_topk_candidates`` sorts by;
+        the score is the one ``similarity()`` would have stored.  Returns the counters int32 [B, 2] (candidates seen, non-finite
+        seen).  Issued where ``similarity()`` is issued, behind ``wait_post()``: it clears the counters and rewrites the lists the
+        previous post-process reads.  The lists hold the next power of two >= max(sparse_cap, nms_pre) keys per image (so ``sparse_cap``
+        = 1024 with ``nms_pre`` = 30000 means 32768) and only ever grow: a later call with a smaller ``sparse_cap`` keeps the larger lists.
+
+        One shared bank of at least SIM_SPLIT_MIN rows on an fp16x3 tower: ``wd_sparse_similarity_split`` — the similarity GEMM with
+        a candidate epilogue, class chunks of 2^20 rows; ``self.scores`` is neither used nor grown.  Everything else (smaller
+        banks, ``precision='fp32'``, the fp32 fallback, per-image banks): the similarity launch of that path into ``self.scores``
+        in class chunks of at most 4096 columns, then ``wd_sparse_rows``; ``self.scores`` never exceeds B * N * 4096 floats here."""
+        from . import sparse as SP
+        self.wait_post()
+        rows = self.B * self.ntot
+        cap = SP.list_capacity(sparse_cap, self.nms_pre)
+        if self._sparse_list is not None and self._sparse_list.shape[1] >= cap:
+            cap = int(self._sparse_list.shape[1])            # the list only ever grows: a smaller request runs with the room there is
+        else:
+            if self._sparse_list is not None and self.post_stream is not None:
+                self._sparse_list.record_stream(self.post_stream)     # the previous post-process sorted it there
+            self._sparse_list = torch.empty(self.B, cap, dtype=torch.int64, device=self.dev)
+            if self._sparse_state is None:
+                self._sparse_state = torch.empty(self.B, 2, dtype=torch.int32, device=self.dev)
+                self._sparse_status = torch.empty(self.B, dtype=torch.int32, device=self.dev)
+                self._sparse_seen = torch.empty(self.B, dtype=torch.int32, device=self.dev)
+        lst, state = self._sparse_list, self._sparse_state
+        state.zero_()
+        thr = float(np.float32(score_thr))
+        seg = (self.ntot, self.off[1], self.off[2], self.lvl_scale, self.lvl_bias)
+        self._scores_fold = None
+        if text.dim() == 3 or text_counts is not None:
+            if not isinstance(text, torch.Tensor) or text.dim() != 3:
+                raise L.WedetectHipError("per-image text banks must be one device float32 [B, k_max, 768] tensor on the tower's device")
+            k = int(text.shape[1])
+            for c0 in range(0, k, SP.ROWS_CHUNK):
+                kc = min(SP.ROWS_CHUNK, k - c0)
+                sub, cnt = text, text_counts
+                if kc != k:
+                    sub = text[:, c0:c0 + kc].contiguous()
+                    cnt = None if text_counts is None else (text_counts - c0).clamp_(0, kc).to(torch.int32)
+                out = self._similarity_per_image(sub, normalize, True, cnt)
+                SP.sparse_rows(out, self.B, self.ntot, kc, kc, k, thr, lst, cap, state, c0, cnt)
+            return state
+        k = int(text.shape[0])
+        if text.dtype != torch.float32 or text.dim() != 2 or text.shape[1] != EMBED_DIM or not text.is_cuda:
+            raise L.WedetectHipError("text bank must be a device float32 [K, 768] tensor")
+        t = text.contiguous()
+        if self._embed_split_valid and self.precision == "fp16x3" and self.want_sim_split(k):
+            if k > self.text_norm.shape[0]:
+                self.text_norm = torch.empty(k, EMBED_DIM, dtype=torch.float32, device=self.dev)
+                self.generation += 1
+            ts = self._split_text(t, normalize)
+            if ts is not None:
+                unscale = ts[1] / self.sscale.get("embed", 1.0)
+                for c0 in range(0, k, SP.FUSED_CHUNK):
+                    SP.sparse_similarity_split(self.embed_s, rows, ts[0], unscale, min(SP.FUSED_CHUNK, k - c0), EMBED_DIM, self.ntot, k, thr,
+                                               lst, cap, state, cls_offset=c0, seg=seg, range_flag=self.range_flag, t_row=c0)
+                return state
+        kmax = min(k, SP.ROWS_CHUNK)
+        if kmax > self.max_classes:
+            self._alloc_post(kmax)
+        if normalize:
+            if k > self.text_norm.shape[0]:
+                self.text_norm = torch.empty(k, EMBED_DIM, dtype=torch.float32, device=self.dev)
+                self.generation += 1
+            L.l2norm_rows(t, self.text_norm[:k])
+            t = self.text_norm[:k]
+        for c0 in range(0, k, SP.ROWS_CHUNK):
+            kc = min(SP.ROWS_CHUNK, k - c0)
+            out = self.scores.view(-1)[: rows * kc].view(self.B, self.ntot, kc)
+            L.conv_gemm(self._embed, t[c0:c0 + kc], None, out, batch=1, hin=1, win=rows, cin=EMBED_DIM, lda=EMBED_DIM,
+                        n=kc, ldc=kc, sigmoid=True, seg=seg)
+            SP.sparse_rows(out, self.B, self.ntot, kc, kc, k, thr, lst, cap, state, c0)
+        return state
+
+    def postprocess_sparse(self, text: torch.Tensor, meta: torch.Tensor, iou_thr: float = 0.7, with_embed: bool = True,
+                           nms: str = "vanilla", nms_param: Optional[int] = None, nms_device: str = "cpu") -> Dict[str, torch.Tensor]:
+        """``postprocess()`` of a ``sparse_candidates()`` step: ``wd_sparse_select`` sorts every image's list into the candidate
+        buffers ``wd_topk_candidates`` would have written, then ``wd_nms_gather`` as ever.  ``text`` only names K.  The usual result
+        fields plus ``sparse_status`` int32 [B] (0 complete, 1 the list overflowed — the image has no rows, 2 non-finite — count
+        -1) and ``sparse_seen`` int32 [B] (candidates seen), device tensors."""
+        from . import sparse as SP
+        B, n, k = self.B, self.ntot, int(text.shape[-2])
+        mode = self.NMS_MODES[nms]
+        if nms_param is None:
+            nms_param = {L.NMS_VANILLA: 0, L.NMS_TORCHVISION: L.TV_TRICK_MAX_NUMEL[nms_device], L.NMS_MMCV: L.MMCV_SPLIT_THR}[mode]
+        SP.sparse_select(self._sparse_list, self._sparse_list.shape[1], self._sparse_state, B, self.nms_pre, self.cand_idx, self.cand_score,
+                         self.cand_count, self._sparse_status)
+        # the counters are cleared by the NEXT step's producers, ahead of its post-process: what is returned is a copy made here, which
+        # — like every other returned tensor — is only overwritten by the next post-process, on this stream
+        self._sparse_seen.copy_(self._sparse_state[:, 0])
+        if with_embed and not self._embed_valid:
+            self._materialise_embed()
+        L.nms_gather(self.cand_idx, self.cand_score, self.cand_count, self.cap, self.boxes, n, k, meta,
+                     L.nms_threshold(iou_thr, mode, nms_device), self.max_out, self._embed if with_embed else None, EMBED_DIM,
+                     self.out_boxes, self.out_scores, self.out_labels, self.out_anchors, self.out_count,
+                     self.out_embed if with_embed else None, B, nms_mode=mode, mode_param=int(nms_param), workspace=self.nms_ws)
+        res = dict(bboxes=self.out_boxes, scores=self.out_scores, labels=self.out_labels, anchors=self.out_anchors,
+                   count=self.out_count, sparse_status=self._sparse_status, sparse_seen=self._sparse_seen)
+        if with_embed:
+            res["embeddings"] = self.out_embed
+        return res
+
+    def _sparse_wanted(self, text: torch.Tensor, score_thr: float) -> bool:
+        """Does this ``sparse_scores=True`` call run sparse?  Not while checked_counts() re-runs an overflowed step, and not for a
+        (bank, threshold) whose lists overflowed in two consecutive steps (``sparse_declined`` counts those calls); a new bank or
+        threshold starts afresh."""
+        key = (text.data_ptr(), text._version, tuple(text.shape), float(np.float32(score_thr)))
+        if key != self._sparse_key:
+            self._sparse_key, self._sparse_streak, self._sparse_off = key, 0, False
+        if self._sparse_dense_once:
+            return False
+        if self._sparse_off:
+            self.sparse_declined += 1
+            return False
+        return True
+
     # ------------------------------------------------------------------ fp16x3 range calibration
     SCALE_TARGET_LOG2 = 10       # calibrate() places max |x| of every split tensor at 2^10: 2^6 of headroom below the fp16 maximum
 
@@ -1673,7 +1807,7 @@ class ImageTower:
     def detect(self, images_u8, text, meta, *, normalize_text: bool, score_thr: float, iou_thr: float = 0.7,
                with_embed: bool = False, nms: Optional[str] = None, nms_param: Optional[int] = None, nms_device: str = "cpu",
                overlap_post: bool = False, text_counts: Optional[torch.Tensor] = None, best_class: bool = False,
-               agnostic_nms: bool = False):
+               agnostic_nms: bool = False, sparse_scores: bool = False, sparse_cap: int = 65536):
         """The whole step.  ``text`` [K, 768] (one bank) or [B, k_max, 768] with ``text_counts`` (one bank per image, see
         similarity(); in line and under ``overlap_post`` alike, same bits).  ``nms`` None picks the library the reference's path of this text handling uses: normalised
         text = BNContrastiveHead of the mmdet path -> "mmcv"; prompts as stored = the Uni scripts -> "torchvision".
@@ -1695,7 +1829,16 @@ class ImageTower:
         stands where ``similarity()`` stands and ``postprocess_best()`` where ``postprocess()`` stands; same streams, same result
         fields, in line and pipelined alike.  The step runs eagerly on the unfolded head.  ``agnostic_nms`` (with ``best_class``
         and the mmcv form): ``mmcv.ops.batched_nms(..., class_agnostic=True)`` — un-offset boxes, one NMS across all labels
-        below split_thr candidates."""
+        below split_thr candidates.
+
+        ``sparse_scores``: the multi-label step with identical semantics whose similarity launch writes the candidates
+        (score > score_thr) to per-image lists of ``sparse_cap`` keys instead of the [B, N, K] scores: ``sparse_candidates()`` stands
+        where ``similarity()`` stands and ``postprocess_sparse()`` where ``postprocess()`` stands.  Where no list overflows the
+        result is the dense step's, bit for bit; the result carries ``sparse_status`` / ``sparse_seen`` and ``checked_counts()``
+        re-runs an overflowed step densely.  Eager, on the unfolded head; exclusive with ``best_class``."""
+        if sparse_scores and best_class:
+            raise ValueError("sparse_scores=True is the multi-label step; best_class=True is the single-label one: choose one")
+        sparse = bool(sparse_scores) and self._sparse_wanted(text, score_thr)
         if nms is None:
             nms = "mmcv" if normalize_text else "torchvision"
         if agnostic_nms and not best_class:
@@ -1706,14 +1849,18 @@ class ImageTower:
         num_classes = None if (text.dim() == 3 or text_counts is not None) else text.shape[0]
         # the bank folded into the embedding conv (None: this step runs the unfolded path); folded here, on the caller's stream,
         # ahead of the backbone every later stream of the step waits for
-        fold = None if best_class else self._fold_for(text, text_counts, normalize_text)
+        fold = None if (best_class or sparse) else self._fold_for(text, text_counts, normalize_text)
         post_best = lambda: self.postprocess_best(text, score_thr, meta, iou_thr, with_embed, nms, nms_param, nms_device, agnostic_nms)
+        post_sparse = lambda: self.postprocess_sparse(text, meta, iou_thr, with_embed, nms, nms_param, nms_device)
         if not overlap_post:
             self.wait_post(reads=True)            # a pipelined step, or the caller on the post stream, may still be reading the buffers this one is about to write
             self.features(images_u8, num_classes=num_classes, _fold=fold)
             if best_class:
                 self.best_scores(text, normalize=normalize_text, text_counts=text_counts)
                 return post_best()
+            if sparse:
+                self.sparse_candidates(text, normalize_text, score_thr, text_counts=text_counts, sparse_cap=sparse_cap)
+                return post_sparse()
             scores = self.similarity(text, normalize=normalize_text, text_counts=text_counts, _fold=fold)
             self._mark_c2(fold)
             return self.postprocess(scores, score_thr, meta, iou_thr, with_embed, nms, nms_param, nms_device)
@@ -1760,6 +1907,9 @@ class ImageTower:
                 if best_class:
                     scores = None
                     self.best_scores(text, normalize=normalize_text, text_counts=text_counts)
+                elif sparse:
+                    scores = None
+                    self.sparse_candidates(text, normalize_text, score_thr, text_counts=text_counts, sparse_cap=sparse_cap)
                 else:
                     scores = self.similarity(text, normalize=normalize_text, text_counts=text_counts, _fold=fold)
                 self._mark_c2(fold)
@@ -1779,7 +1929,10 @@ class ImageTower:
                     t_.record_stream(nh)
         with torch.cuda.stream(self.post_stream):
             self.post_stream.wait_event(self._post_ready)
-            res = post_best() if best_class else self.postprocess(scores, score_thr, meta, iou_thr, with_embed, nms, nms_param, nms_device)
+            if sparse:
+                res = post_sparse()
+            else:
+                res = post_best() if best_class else self.postprocess(scores, score_thr, meta, iou_thr, with_embed, nms, nms_param, nms_device)
             if self._post_done is None:
                 self._post_done = torch.cuda.Event()
             self._post_done.record(self.post_stream)
@@ -1890,6 +2043,34 @@ class ImageTower:
         else:
             cur.wait_event(self._post_done)
 
+    def _sparse_checked(self, res: Dict[str, torch.Tensor], rerun, recalibrate) -> Tuple[Optional[List[int]], List[int]]:
+        """The sparse part of ``checked_counts()``: the select status is read with the counts (one small device concatenation, one
+        copy, the same synchronisation point).  An overflowed image (status 1): ``sparse_overflows`` counts the step and ``rerun()`` is
+        executed once with the dense path (its result replaces this one in the tower's buffers); after two consecutive overflowed
+        steps the tower stops trying sparse for this (bank, threshold), with one warning.  Returns (the final counts of that re-run,
+        or None: no overflow — the caller goes on with the range guard; status 2 shows there as a count of -1 and its re-run stays
+        sparse, through ``wd_sparse_rows`` on an fp32 tower; this step's counts)."""
+        both = torch.cat([res["count"], res["sparse_status"]]).tolist()
+        counts, status = both[: len(both) // 2], both[len(both) // 2:]
+        if 1 not in status:
+            self._sparse_streak = 0
+            return None, counts
+        if not self._sparse_step_counted:                    # a step that overflows again in a re-run (range trip in between) counts once
+            self._sparse_step_counted = True
+            self.sparse_overflows += 1
+            self._sparse_streak += 1
+        if self._sparse_streak >= 2 and not self._sparse_off:
+            self._sparse_off = True
+            import warnings
+            warnings.warn("wedetect_amd: the sparse candidate lists overflowed in two consecutive steps; this bank and threshold run "
+                          "the dense multi-label step from now on (a larger sparse_cap or a higher score_thr avoids it)")
+        self._sparse_dense_once = True
+        try:
+            dense = rerun()
+        finally:
+            self._sparse_dense_once = False
+        return self.checked_counts(dense, rerun, recalibrate), counts
+
     def checked_counts(self, res: Dict[str, torch.Tensor], rerun, recalibrate=None) -> List[int]:
         """Kept-row counts of a step on the host (the one D2H sync a caller needs anyway) with the fp16x3 range guard:
         the fp16x3 GEMMs carry fp32 operands as fp16 (hi, lo) pairs, so an activation beyond 65504 becomes inf.  Every
@@ -1902,8 +2083,23 @@ class ImageTower:
         scales from THIS batch (detector._TowerHolder.recalibrate: scales only ever go down, every tower of the checkpoint
         adopts them); it is tried once per trip before the fp32 fallback — a first batch of blank images may have chosen
         scales under which an ordinary image overflows, which is a calibration problem, not a checkpoint that needs fp32."""
+        if self._cc_depth == 0:
+            self._sparse_step_counted = False
+        self._cc_depth += 1
+        try:
+            return self._checked_counts(res, rerun, recalibrate)
+        finally:
+            self._cc_depth -= 1
+
+    def _checked_counts(self, res: Dict[str, torch.Tensor], rerun, recalibrate=None) -> List[int]:
         self.wait_post()                         # a pipelined step's counts are produced on post_stream: order the read behind it
-        counts = res["count"].tolist()
+        counts = None
+        if "sparse_status" in res:
+            done, counts = self._sparse_checked(res, rerun, recalibrate)
+            if done is not None:
+                return done
+        if counts is None:
+            counts = res["count"].tolist()
         if self.overflowed and self.precision == "fp32" and min(counts, default=0) >= 0:
             # round 6: the fallback is no longer for good.  After FALLBACK_RETRY clean fp32 batches (doubling after every further
             # trip, capped) the tower re-derives its split scales from the CURRENT batch (scales only go down) and returns to the
@@ -1949,7 +2145,15 @@ class ImageTower:
         self.overflowed = True
         self._clean_fp32_steps = 0
         self._retry_after = min(self.FALLBACK_RETRY_MAX, self.FALLBACK_RETRY if self.fp16x3_retries == 0 else 2 * self._retry_after)
-        counts = rerun()["count"].tolist()
+        res = rerun()
+        if "sparse_status" in res:
+            # the re-run of a sparse step is sparse again (wd_sparse_rows on the fp32 kernels), and it is the first time an overflow of
+            # an image that was non-finite before can show (status 2 hides status 1): its status is read like any other step's
+            done, counts = self._sparse_checked(res, rerun, recalibrate)
+            if done is not None:
+                return done                                  # the dense re-run's counts, already held to the fp32 rule below
+        else:
+            counts = res["count"].tolist()
         if min(counts, default=0) < 0:
             raise L.WedetectHipError("non-finite scores in fp32 mode: the checkpoint or the inputs produce inf / NaN")
         return counts
