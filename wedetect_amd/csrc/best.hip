@@ -55,25 +55,11 @@ extern "C" int wd_best_similarity_split(const void* e_split, int64_t rows, const
                                         int32_t dim, int32_t seg_rows, int32_t seg_end0, int32_t seg_end1, const float* seg_scale,
                                         const float* seg_bias, uint32_t* range_flag, int32_t cls_offset, uint64_t* key,
                                         void* stream) {
-  if (!e_split || !t_split || !key || rows <= 0 || rows > 0x7ffffff0LL || n_cls <= 0 || dim <= 0 || !(unscale > 0.f))
+  WdConvGemm p;
+  if (wd_similarity_problem(p, e_split, rows, t_split, unscale, n_cls, dim, seg_rows, seg_end0, seg_end1, seg_scale, seg_bias, 1, range_flag) != WD_OK)
     return WD_ERR_BAD_ARG;
-  if (cls_offset < 0 || (long long)cls_offset + n_cls > 0x7fffffffLL || (reinterpret_cast<uintptr_t>(key) & 7u)) return WD_ERR_BAD_ARG;
-  if (seg_rows < 0 || (seg_rows > 0 && (!seg_scale || !seg_bias || !(0 <= seg_end0 && seg_end0 <= seg_end1 && seg_end1 <= seg_rows))))
-    return WD_ERR_BAD_ARG;
+  if (!key || cls_offset < 0 || (long long)cls_offset + n_cls > 0x7fffffffLL || (reinterpret_cast<uintptr_t>(key) & 7u)) return WD_ERR_BAD_ARG;
   if ((unsigned long long)((n_cls + 7) & ~7) * (unsigned long long)((dim + 15) / 16 * 16) * 4ull >= (1ull << 32)) return WD_ERR_UNSUPPORTED;
-  WdConvGemm p{};
-  p.a = static_cast<const float*>(e_split);
-  p.batch = 1; p.hin = 1; p.win = (int)rows; p.cin = dim; p.lda = dim;
-  p.kh = p.kw = p.stride = 1; p.hout = 1; p.wout = (int)rows;
-  p.m = (int)rows; p.n = n_cls; p.k = dim;
-  p.out_scale = 1.0f;
-  p.sigmoid = 1;
-  p.seg_rows = seg_rows; p.seg_end0 = seg_end0; p.seg_end1 = seg_end1;
-  for (int i = 0; i < 3; ++i) {
-    p.seg_scale[i] = seg_rows > 0 ? seg_scale[i] : 1.0f;
-    p.seg_bias[i] = seg_rows > 0 ? seg_bias[i] : 0.0f;
-  }
-  p.range_flag = range_flag;
   return wd_launch_p8_best(p, t_split, unscale, reinterpret_cast<unsigned long long*>(key), cls_offset,
                            static_cast<hipStream_t>(stream));
 }

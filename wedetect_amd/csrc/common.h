@@ -53,6 +53,32 @@ static inline int wd_set_max_lds(WdAttrOnce& once, const void* fn, int bytes) {
 
 static inline bool wd_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// The problem of a rows x classes similarity launch on the pre-split 256 x 256 kernel — wd_similarity_split and its best-class and
+// candidate forms (wd_best_similarity_split, wd_sparse_similarity_split): region rows [rows][dim] as fp16 hi/lo groups, one output
+// column per bank row, the per-level affine of the seg_* group (seg_rows == 0: none).  Checks the arguments the three entries
+// share — WD_ERR_BAD_ARG — and fills ``p``; the output (p.c / p.ldc, or the form's own sink) is the caller's.
+static inline int wd_similarity_problem(WdConvGemm& p, const void* e_split, int64_t rows, const void* t_split, float unscale, int32_t n_cls,
+                                        int32_t dim, int32_t seg_rows, int32_t seg_end0, int32_t seg_end1, const float* seg_scale,
+                                        const float* seg_bias, int32_t sigmoid, uint32_t* range_flag) {
+  if (!e_split || !t_split || rows <= 0 || rows > 0x7ffffff0LL || n_cls <= 0 || dim <= 0 || !(unscale > 0.f)) return WD_ERR_BAD_ARG;
+  if (seg_rows < 0 || (seg_rows > 0 && (!seg_scale || !seg_bias || !(0 <= seg_end0 && seg_end0 <= seg_end1 && seg_end1 <= seg_rows))))
+    return WD_ERR_BAD_ARG;
+  p = WdConvGemm{};
+  p.a = static_cast<const float*>(e_split);
+  p.batch = 1; p.hin = 1; p.win = (int)rows; p.cin = dim; p.lda = dim;
+  p.kh = p.kw = p.stride = 1; p.hout = 1; p.wout = (int)rows;
+  p.m = (int)rows; p.n = n_cls; p.k = dim;
+  p.out_scale = 1.0f;
+  p.sigmoid = sigmoid ? 1 : 0;
+  p.seg_rows = seg_rows; p.seg_end0 = seg_end0; p.seg_end1 = seg_end1;
+  for (int i = 0; i < 3; ++i) {
+    p.seg_scale[i] = seg_rows > 0 ? seg_scale[i] : 1.0f;
+    p.seg_bias[i] = seg_rows > 0 ? seg_bias[i] : 0.0f;
+  }
+  p.range_flag = range_flag;
+  return WD_OK;
+}
+
 __device__ __forceinline__ float wd_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
 // GEMM-epilogue variant: hardware exp2 / rcp (<= 2 ulp, i.e. <= 1.2e-7 absolute on a score), a third of the
 // instructions of the exact form — the similarity GEMM's epilogue is 20 sigmoids per lane

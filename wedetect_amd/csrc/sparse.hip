@@ -142,26 +142,13 @@ extern "C" int wd_sparse_similarity_split(const void* e_split, int64_t rows, con
                                           const float* seg_bias, uint32_t* range_flag, int32_t cls_offset, int32_t rows_per_img,
                                           int32_t n_cls_total, float thr, uint64_t* list, int32_t list_cap, int32_t* state,
                                           void* stream) {
-  if (!e_split || !t_split || rows <= 0 || rows > 0x7ffffff0LL || n_cls <= 0 || dim <= 0 || !(unscale > 0.f)) return WD_ERR_BAD_ARG;
+  WdConvGemm p;
+  if (wd_similarity_problem(p, e_split, rows, t_split, unscale, n_cls, dim, seg_rows, seg_end0, seg_end1, seg_scale, seg_bias, 1, range_flag) != WD_OK)
+    return WD_ERR_BAD_ARG;
   if (bad_list(list, list_cap, state) || rows_per_img <= 0 || rows % rows_per_img || n_cls_total <= 0) return WD_ERR_BAD_ARG;
   if (cls_offset < 0 || (long long)cls_offset + n_cls > (long long)n_cls_total) return WD_ERR_BAD_ARG;
-  if (seg_rows < 0 || (seg_rows > 0 && (!seg_scale || !seg_bias || !(0 <= seg_end0 && seg_end0 <= seg_end1 && seg_end1 <= seg_rows))))
-    return WD_ERR_BAD_ARG;
   if ((long long)rows_per_img * n_cls_total >= (1LL << 31)) return WD_ERR_UNSUPPORTED;
   if ((unsigned long long)((n_cls + 7) & ~7) * (unsigned long long)((dim + 15) / 16 * 16) * 4ull >= (1ull << 32)) return WD_ERR_UNSUPPORTED;
-  WdConvGemm p{};
-  p.a = static_cast<const float*>(e_split);
-  p.batch = 1; p.hin = 1; p.win = (int)rows; p.cin = dim; p.lda = dim;
-  p.kh = p.kw = p.stride = 1; p.hout = 1; p.wout = (int)rows;
-  p.m = (int)rows; p.n = n_cls; p.k = dim;
-  p.out_scale = 1.0f;
-  p.sigmoid = 1;
-  p.seg_rows = seg_rows; p.seg_end0 = seg_end0; p.seg_end1 = seg_end1;
-  for (int i = 0; i < 3; ++i) {
-    p.seg_scale[i] = seg_rows > 0 ? seg_scale[i] : 1.0f;
-    p.seg_bias[i] = seg_rows > 0 ? seg_bias[i] : 0.0f;
-  }
-  p.range_flag = range_flag;
   return wd_launch_p8_sparse(p, t_split, unscale, reinterpret_cast<unsigned long long*>(list), list_cap, state, rows_per_img,
                              n_cls_total, cls_offset, thr, static_cast<hipStream_t>(stream));
 }

@@ -117,12 +117,15 @@ struct P8Persist {
 // row-tile group (five times for 32 images x 300 regions), the region rows (29 MB) stay in the Infinity Cache.
 constexpr int P8VAR_RETR = 4096;
 constexpr int P8VAR_DIRECT = 8192;      // with SVAR_CSPLIT: the direct (no LDS transpose) hi/lo epilogue; GELU / no activation only
+// One argument block for the epilogues that do not store the product; a launch fills its own members.  RETR: scale, bias [region rows]
+// (logit scale applied as exp(scale)); count [images]: valid rows of an image (the first count[i] of its rows_per_img); out [images][ldo]
+// zero-filled: max over an image's valid rows of sigmoid(<e, t> exp(scale) + bias).  BEST / SPARSE: see their epilogues below.
 struct P8Retr {
-  const float* scale;    // [region rows]: logit scale of a row, applied as exp(scale)
-  const float* bias;     // [region rows]
-  const int* count;      // [images]: valid rows of an image (the first count[i] of its rows_per_img)
-  float* out;            // [images][ldo] zero-filled: max over an image's valid rows of sigmoid(<e, t> exp(scale) + bias)
-  int rows_per_img, ldo, n_cls_total, list_cap; float thr;   // n_cls_total / list_cap / thr: sparse candidates (P8VAR_SPARSE) only
+  const float *scale, *bias;
+  union { const int* count; int* state; };
+  union { float* out; unsigned long long* key; unsigned long long* list; };
+  int rows_per_img; union { int ldo; int cls_offset; };
+  int n_cls_total, list_cap; float thr;
 };
 
 template <int TM, int TN>
@@ -201,6 +204,7 @@ __device__ __forceinline__ void p8_best_epilogue(const WdConvGemm& p, unsigned l
 
 constexpr int P8VAR_SPARSE = 32768;     // candidates above a threshold (wd_sparse_similarity_split): p8_sparse_epilogue, at the end of this file
 template <int TM, int TN> __device__ __forceinline__ void p8_sparse_epilogue(const WdConvGemm& p, const P8Retr& rt, float unscale, int mw, int nw, int lane, const f32x16 (&acc)[TM][TN]);
+
 template <int VAR, int ABL = 0, bool PERSIST = false>
 __global__ void __launch_bounds__(512, 2)
 split_gemm_p8_kernel(const WdConvGemm p, const unsigned char* __restrict__ wsp, int k16, float unscale, int nbn,
@@ -520,11 +524,8 @@ split_gemm_p8_kernel(const WdConvGemm p, const unsigned char* __restrict__ wsp, 
       p8_retr_epilogue<TM, TN>(p, rt, unscale, m0 + group * 128, n0 + wn * 64, lane, acc);
       continue;
     }
-    if constexpr ((VAR & P8VAR_BEST) != 0) {                        // key pointer / cls_offset travel in rt.out / rt.ldo
-      p8_best_epilogue<TM, TN>(p, reinterpret_cast<unsigned long long*>(rt.out), rt.ldo, unscale, m0 + group * 128, n0 + wn * 64, lane, acc);
-      continue;
-    }
-    if constexpr ((VAR & P8VAR_SPARSE) != 0) { p8_sparse_epilogue<TM, TN>(p, rt, unscale, m0 + group * 128, n0 + wn * 64, lane, acc); continue; }   // list / state / cls_offset travel in rt.out / rt.count / rt.ldo
+    if constexpr ((VAR & P8VAR_BEST) != 0) { p8_best_epilogue<TM, TN>(p, rt.key, rt.cls_offset, unscale, m0 + group * 128, n0 + wn * 64, lane, acc); continue; }
+    if constexpr ((VAR & P8VAR_SPARSE) != 0) { p8_sparse_epilogue<TM, TN>(p, rt, unscale, m0 + group * 128, n0 + wn * 64, lane, acc); continue; }
     const EpiVec ev{vec_c, vec_res, vec_bias, unscale};
     const int mw = m0 + group * 128, nw = n0 + wn * 64;
     float* patch = reinterpret_cast<float*>(smem_raw) + wave * 32 * EPI_LDT;
@@ -714,20 +715,41 @@ int wd_launch_p8_retrieval(const void* t_split, int n_cls, const void* e_split, 
   p.m = n_cls; p.n = n_rows; p.k = dim; p.ldc = ldo;
   p.out_scale = 1.0f;
   p.range_flag = range_flag;
-  return launch_p8_retr(p, e_split, unscale, P8Retr{scale, bias, count, out, rows_per_img, ldo}, st);
+  return launch_p8_retr(p, e_split, unscale, P8Retr{scale, bias, {count}, {out}, rows_per_img, {ldo}}, st);
 }
 
 // wd_similarity_split on the 256 x 256 kernel (round 6; yolo_world_head.py:90-108, generate_proposal.py:1129-1131): region rows
 // [rows][dim] as fp16 hi/lo groups (buffer padded to a multiple of eight rows) x text rows [n_cls][dim] split by
 // wd_split_weights_padded; out[row][cls] = (sigmoid)(<e, t> * unscale * seg_scale[level(row)] + seg_bias[level(row)]), the
 // epilogue of the fp32 similarity GEMM.  Ragged n_cls (1203) and ldo are fine (scalar stores when ldo % 4).
+// the three similarity launches: K in whole 32-column steps, row groups of eight, aligned bases, no epilogue but affine + sigmoid
+static bool p8_similarity_ok(const WdConvGemm& p, const void* t_split) {
+  if (p.k % 32 || p.k < 32 || p.lda % 8 || !wd_aligned16(p.a) || !wd_aligned16(t_split)) return false;
+  return !(p.res || p.c2 || p.bias || p.act != WD_ACT_NONE || p.out_mode != WD_OUT_ROWS || p.c_batch_stride > 0 || p.ln_stats);
+}
+
 int wd_launch_p8_similarity(const WdConvGemm& p, const void* t_split, float unscale, hipStream_t st) {
-  if (p.k % 32 || p.k < 32 || p.lda % 8 || !wd_aligned16(p.a) || !wd_aligned16(t_split)) return WD_ERR_UNSUPPORTED;
-  if (p.res || p.c2 || p.bias || p.act != WD_ACT_NONE || p.out_mode != WD_OUT_ROWS || p.c_batch_stride > 0 || p.ln_stats) return WD_ERR_UNSUPPORTED;
+  if (!p8_similarity_ok(p, t_split)) return WD_ERR_UNSUPPORTED;
   return launch_p8<0>(p, t_split, unscale, st, nullptr, 0, (p.m + 7) & ~7, (p.n + 7) & ~7);
 }
 
 namespace {
+
+// The members of P8Retr the two epilogues below read: BEST key [region rows], cls_offset (the class of the launch's first bank row);
+// SPARSE list [images][list_cap], state [images][2], rows_per_img, cls_offset, n_cls_total, thr (csrc/sparse.hip).
+// the argument block of split_gemm_p8_kernel, pinned byte for byte: the members of a union share one slot
+static_assert(sizeof(P8Retr) == 56 && offsetof(P8Retr, scale) == 0 && offsetof(P8Retr, bias) == 8 && offsetof(P8Retr, count) == 16 &&
+              offsetof(P8Retr, state) == 16 && offsetof(P8Retr, out) == 24 && offsetof(P8Retr, key) == 24 && offsetof(P8Retr, list) == 24 &&
+              offsetof(P8Retr, rows_per_img) == 32 && offsetof(P8Retr, ldo) == 36 && offsetof(P8Retr, cls_offset) == 36 &&
+              offsetof(P8Retr, n_cls_total) == 40 && offsetof(P8Retr, list_cap) == 44 && offsetof(P8Retr, thr) == 48, "P8Retr layout");
+
+// The score of accumulator element v of a row, for the two epilogues below: the expressions of the materialising epilogue
+// (epi_quad<WD_ACT_NONE, true>), so the bits it would have stored.
+__device__ __forceinline__ float p8_score(float v, float unscale, const EpiRow& er) {
+  float x = fmaf(v, unscale, 0.0f);                                // unscale is a power of two: exact
+  x = fmaf(x, er.oscale, er.obias);
+  return wd_sigmoid_fast(x);
+}
 
 // ---- best class per region row on this kernel (wd_best_similarity_split, include/wedetect_hip_best.h) -----------------------
 // The similarity launch with another epilogue; operands NOT swapped: in the accumulator layout the region row is the LANE
@@ -739,8 +761,7 @@ namespace {
 // exchange with the other half-wave, then ONE 64-bit vector atomic max per (row, wave) into key[row] — max is order-independent:
 // the result does not depend on the tile order or on how the bank is cut into launches.  A row with a non-finite accumulator
 // (an fp16 half that overflowed) gets NaN score bits, which beat every score: the unpacked score is then non-finite and
-// wd_topk_candidates reports the image.  The key pointer and cls_offset travel in P8Retr.out / P8Retr.ldo.  (Defined behind its
-// use: the template is declared in front of the kernel.)
+// wd_topk_candidates reports the image.  (Defined behind its use: the template is declared in front of the kernel.)
 __device__ __forceinline__ unsigned long long p8_umax64(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
 
 template <int TM, int TN>
@@ -764,9 +785,7 @@ __device__ __forceinline__ void p8_best_epilogue(const WdConvGemm& p, unsigned l
         if (cq < p.n && m < p.m) bad |= wd_any_nonfinite4(acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          float x = fmaf(acc[i][j][4 * g + q], unscale, 0.0f);     // unscale is a power of two: exact
-          x = fmaf(x, er.oscale, er.obias);
-          x = wd_sigmoid_fast(x);
+          const float x = p8_score(acc[i][j][4 * g + q], unscale, er);
           const unsigned long long kq = ((unsigned long long)__float_as_uint(x) << 32) | (unsigned long long)(inv0 - (unsigned)(32 * j + 8 * g + q));
           best = p8_umax64(best, cq + q < p.n ? kq : 0ull);
         }
@@ -786,12 +805,10 @@ __device__ __forceinline__ void p8_best_epilogue(const WdConvGemm& p, unsigned l
 // wd_best_similarity_split: the launch above with the best-class epilogue (p8_best_epilogue) in place of the stores; p.c is unused.
 // The caller has checked n_cls * k16 * 4 < 2^32 (launch_p8 refuses it too: 32-bit DMA offsets from the operand base).
 int wd_launch_p8_best(const WdConvGemm& p, const void* t_split, float unscale, unsigned long long* key, int cls_offset, hipStream_t st) {
-  if (p.k % 32 || p.k < 32 || p.lda % 8 || !wd_aligned16(p.a) || !wd_aligned16(t_split) || !key || (reinterpret_cast<uintptr_t>(key) & 7u))
-    return WD_ERR_UNSUPPORTED;
-  if (p.res || p.c2 || p.bias || p.act != WD_ACT_NONE || p.out_mode != WD_OUT_ROWS || p.c_batch_stride > 0 || p.ln_stats || !p.sigmoid)
-    return WD_ERR_UNSUPPORTED;
-  return launch_p8<P8VAR_BEST>(p, t_split, unscale, st, nullptr, 0, (p.m + 7) & ~7, (p.n + 7) & ~7,
-                               P8Retr{nullptr, nullptr, nullptr, reinterpret_cast<float*>(key), 0, cls_offset});
+  if (!p8_similarity_ok(p, t_split) || !p.sigmoid || !key || (reinterpret_cast<uintptr_t>(key) & 7u)) return WD_ERR_UNSUPPORTED;
+  P8Retr rt{};
+  rt.key = key; rt.cls_offset = cls_offset;
+  return launch_p8<P8VAR_BEST>(p, t_split, unscale, st, nullptr, 0, (p.m + 7) & ~7, (p.n + 7) & ~7, rt);
 }
 
 namespace {
@@ -812,8 +829,8 @@ __device__ __forceinline__ void p8_sparse_epilogue(const WdConvGemm& p, const P8
                                                    const f32x16 (&acc)[TM][TN]) {
   static_assert(TN * 16 == 32, "one 32-bit pass mask per (lane, row tile)");
   if (mw >= p.m || nw >= p.n) return;                              // wave-uniform
-  unsigned long long* __restrict__ list = reinterpret_cast<unsigned long long*>(rt.out);
-  int* __restrict__ state = const_cast<int*>(rt.count);
+  unsigned long long* __restrict__ list = rt.list;
+  int* __restrict__ state = rt.state;
   const int rpi = rt.rows_per_img;
   const unsigned cap = (unsigned)rt.list_cap;
   const float thr = rt.thr;
@@ -831,7 +848,7 @@ __device__ __forceinline__ void p8_sparse_epilogue(const WdConvGemm& p, const P8
     const int mc = row_ok ? m : p.m - 1;                           // rows past the end: what the padded buffer holds there is not ours to judge
     const EpiRow er = epi_row<true>(p, mc);
     const int b = one_image ? b_first : mc / rpi;
-    const unsigned flat0 = (unsigned)(mc - b * rpi) * (unsigned)rt.n_cls_total + (unsigned)rt.ldo + (unsigned)c_lane;
+    const unsigned flat0 = (unsigned)(mc - b * rpi) * (unsigned)rt.n_cls_total + (unsigned)rt.cls_offset + (unsigned)c_lane;
     float sc[TN * 16];
     unsigned mask = 0u;
     bool bad = false;
@@ -843,9 +860,7 @@ __device__ __forceinline__ void p8_sparse_epilogue(const WdConvGemm& p, const P8
         if (cq < p.n && row_ok) bad |= wd_any_nonfinite4(acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          float x = fmaf(acc[i][j][4 * g + q], unscale, 0.0f);     // unscale is a power of two: exact
-          x = fmaf(x, er.oscale, er.obias);
-          x = wd_sigmoid_fast(x);
+          const float x = p8_score(acc[i][j][4 * g + q], unscale, er);
           sc[16 * j + 4 * g + q] = x;
           mask |= (row_ok && cq + q < p.n && x > thr) ? (1u << (16 * j + 4 * g + q)) : 0u;
         }
@@ -890,10 +905,9 @@ __device__ __forceinline__ void p8_sparse_epilogue(const WdConvGemm& p, const P8
 // unused.  The caller has checked the sizes (csrc/sparse.hip).
 int wd_launch_p8_sparse(const WdConvGemm& p, const void* t_split, float unscale, unsigned long long* list, int list_cap, int* state,
                         int rows_per_img, int n_cls_total, int cls_offset, float thr, hipStream_t st) {
-  if (p.k % 32 || p.k < 32 || p.lda % 8 || !wd_aligned16(p.a) || !wd_aligned16(t_split) || !list || !state) return WD_ERR_UNSUPPORTED;
-  if (p.res || p.c2 || p.bias || p.act != WD_ACT_NONE || p.out_mode != WD_OUT_ROWS || p.c_batch_stride > 0 || p.ln_stats || !p.sigmoid)
-    return WD_ERR_UNSUPPORTED;
-  return launch_p8<P8VAR_SPARSE>(p, t_split, unscale, st, nullptr, 0, (p.m + 7) & ~7, (p.n + 7) & ~7,
-                                 P8Retr{nullptr, nullptr, state, reinterpret_cast<float*>(list), rows_per_img, cls_offset, n_cls_total,
-                                        list_cap, thr});
+  if (!p8_similarity_ok(p, t_split) || !p.sigmoid || !list || !state) return WD_ERR_UNSUPPORTED;
+  P8Retr rt{};
+  rt.list = list; rt.list_cap = list_cap; rt.state = state;
+  rt.rows_per_img = rows_per_img; rt.n_cls_total = n_cls_total; rt.cls_offset = cls_offset; rt.thr = thr;
+  return launch_p8<P8VAR_SPARSE>(p, t_split, unscale, st, nullptr, 0, (p.m + 7) & ~7, (p.n + 7) & ~7, rt);
 }

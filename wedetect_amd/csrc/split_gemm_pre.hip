@@ -625,24 +625,12 @@ int wd_launch_p8_similarity(const WdConvGemm& p, const void* t_split, float unsc
 extern "C" int wd_similarity_split(const void* e_split, int64_t rows, const void* t_split, float unscale, float* out, int32_t n_cls,
                                    int32_t dim, int32_t ldo, int32_t seg_rows, int32_t seg_end0, int32_t seg_end1,
                                    const float* seg_scale, const float* seg_bias, int32_t sigmoid, uint32_t* range_flag, void* stream) {
-  if (!e_split || !t_split || !out || rows <= 0 || rows > 0x7ffffff0LL || n_cls <= 0 || dim <= 0 || ldo < n_cls || !(unscale > 0.f))
+  WdConvGemm p;
+  if (!out || ldo < n_cls || wd_similarity_problem(p, e_split, rows, t_split, unscale, n_cls, dim, seg_rows, seg_end0, seg_end1, seg_scale, seg_bias,
+                                                   sigmoid, range_flag) != WD_OK)
     return WD_ERR_BAD_ARG;
-  if (seg_rows < 0 || (seg_rows > 0 && (!seg_scale || !seg_bias || !(0 <= seg_end0 && seg_end0 <= seg_end1 && seg_end1 <= seg_rows))))
-    return WD_ERR_BAD_ARG;
-  WdConvGemm p{};
-  p.a = static_cast<const float*>(e_split);
   p.c = out;
-  p.batch = 1; p.hin = 1; p.win = (int)rows; p.cin = dim; p.lda = dim;
-  p.kh = p.kw = p.stride = 1; p.hout = 1; p.wout = (int)rows;
-  p.m = (int)rows; p.n = n_cls; p.k = dim; p.ldc = ldo;
-  p.out_scale = 1.0f;
-  p.sigmoid = sigmoid ? 1 : 0;
-  p.seg_rows = seg_rows; p.seg_end0 = seg_end0; p.seg_end1 = seg_end1;
-  for (int i = 0; i < 3; ++i) {
-    p.seg_scale[i] = seg_rows > 0 ? seg_scale[i] : 1.0f;
-    p.seg_bias[i] = seg_rows > 0 ? seg_bias[i] : 0.0f;
-  }
-  p.range_flag = range_flag;
+  p.ldc = ldo;
   if (!p.sigmoid && p.seg_rows == 0) return WD_ERR_UNSUPPORTED;   // a plain product: wd_conv_gemm_split covers it
   return wd_launch_p8_similarity(p, t_split, unscale, static_cast<hipStream_t>(stream));
 }

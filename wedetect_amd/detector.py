@@ -205,8 +205,8 @@ class _TowerHolder:
         range guard's switch to fp32 therefore captures anew."""
         self.calibrate_first(tower, images_u8)
         if kw.get("best_class") or kw.get("sparse_scores"):
-            # single-label and sparse-score steps run eagerly on the unfolded head (engine.ImageTower.best_scores /
-            # sparse_candidates): no graph, no fold
+            # single-label and sparse-score steps run eagerly on the unfolded head (the best_scores / sparse_candidates sinks of
+            # engine.ImageTower._score_bank): no graph, no fold
             return tower.detect(images_u8, text, meta, text_counts=text_counts, **kw)
         if text.dim() == 3 or text_counts is not None:
             # one bank per image ([B, k_max, 768] + device counts): always the eager step, never captured — a graph would

@@ -1223,66 +1223,124 @@ class ImageTower:
         (the embeddings and the bank are fp32 in both modes)."""
         if text.dim() == 3 or text_counts is not None:
             return self._similarity_per_image(text, normalize, sigmoid, text_counts)
-        k = text.shape[0]
-        if text.dtype != torch.float32 or text.shape[1] != EMBED_DIM or not text.is_cuda:
-            raise L.WedetectHipError("text bank must be a device float32 [K, 768] tensor")
-        if k > self.max_classes:
-            self._alloc_post(k)
-        if k > self.text_norm.shape[0]:
-            self.text_norm = torch.empty(k, EMBED_DIM, dtype=torch.float32, device=self.dev)
-            self.generation += 1
-        t = text.contiguous()
-        out = self.scores.view(-1)[: self.B * self.ntot * k].view(self.B, self.ntot, k)
-        seg = (self.ntot, self.off[1], self.off[2], self.lvl_scale, self.lvl_bias)
-        self._scores_fold = None
         if _fold is not None:                     # detect(): the head stopped at c2 for this fold of ``text``
+            k = self._check_shared_bank(text)
+            out = self._scores_block(k)
+            self._grow_text_norm(k)
             self._similarity_folded(_fold, out, k, sigmoid)
             self._scores_fold = (_fold, bool(sigmoid))
             return out
-        if self._embed_split_valid and self.precision == "fp16x3" and self.want_sim_split(k):
-            ts = self._split_text(t, normalize)
-            if ts is not None:
-                L.similarity_split(self.embed_s, self.B * self.ntot, ts[0], ts[1] / self.sscale.get("embed", 1.0), out, k, EMBED_DIM, k,
-                                   seg=seg, sigmoid=sigmoid, range_flag=self.range_flag)
-                return out
-        if normalize:
-            L.l2norm_rows(t, self.text_norm[:k])
-            t = self.text_norm[:k]
-        L.conv_gemm(self._embed, t, None, out, batch=1, hin=1, win=self.B * self.ntot, cin=EMBED_DIM, lda=EMBED_DIM,
-                    n=k, ldc=k, sigmoid=sigmoid, seg=seg)
-        return out
+        self._score_bank(text, normalize, None, self._dense_sink(sigmoid), whole=True, sigmoid=sigmoid)
+        return self._scores_block(text.shape[0])
 
     def _similarity_per_image(self, text: torch.Tensor, normalize: bool, sigmoid: bool,
                               text_counts: Optional[torch.Tensor]) -> torch.Tensor:
-        if not isinstance(text, torch.Tensor) or text.dim() != 3 or text.dtype != torch.float32 or text.shape[2] != EMBED_DIM \
-                or not text.is_cuda or text.device != self._embed.device or text.shape[1] < 1:
-            raise L.WedetectHipError("per-image text banks must be one device float32 [B, k_max, 768] tensor on the tower's device")
-        if text.shape[0] != self.B:
-            raise L.WedetectHipError(f"per-image text banks: {text.shape[0]} banks for a tower of batch {self.B}")
-        self._per_image_seen = True
-        self._scores_fold = None
-        if text_counts is not None:
-            if not isinstance(text_counts, torch.Tensor) or not text_counts.is_cuda or text_counts.device != self._embed.device:
-                raise L.WedetectHipError("text_counts must be a DEVICE int32 [B] tensor (the kernel reads it; the step has no host read)")
-            if text_counts.dtype != torch.int32 or tuple(text_counts.shape) != (self.B,):
-                raise L.WedetectHipError(f"text_counts must be int32 of shape [{self.B}], got {text_counts.dtype} {tuple(text_counts.shape)}")
-            text_counts = text_counts.contiguous()
-        k = text.shape[1]
-        if k > self.max_classes:
-            self._alloc_post(k)
-        t = text.contiguous()
-        if normalize:
-            # every row on its own, as in the shared path: row (b, c) gets the bits the 2-D call gives that row
-            if self.text_norm_pi is None or self.B * k > self.text_norm_pi.shape[0]:
-                self.text_norm_pi = torch.empty(self.B * k, EMBED_DIM, dtype=torch.float32, device=self.dev)
-                self.generation += 1
-            tn = self.text_norm_pi[: self.B * k]
-            L.l2norm_rows(t.view(self.B * k, EMBED_DIM), tn)
-            t = tn.view(self.B, k, EMBED_DIM)
-        out = self.scores.view(-1)[: self.B * self.ntot * k].view(self.B, self.ntot, k)
+        self._score_bank(text, normalize, text_counts, self._dense_sink(sigmoid), whole=True, sigmoid=sigmoid)
+        return self._scores_block(text.shape[1])
+
+    def _dense_sink(self, sigmoid: bool):
+        """The sink of similarity(): the whole bank is one chunk, the fused kernel stores the scores (wd_similarity_split) and a
+        materialised block is the result as it stands."""
+        def fused(t_split, unscale, kc, c0, seg):
+            L.similarity_split(self.embed_s, self.B * self.ntot, t_split, unscale, self._scores_block(kc), kc, EMBED_DIM, kc,
+                               seg=seg, sigmoid=sigmoid, range_flag=self.range_flag)
+        return fused, lambda out, kc, c0, counts: None, None, None
+
+    # ------------------------------------------------------------------ the score stage: one walk over a bank, three sinks
+    def _check_shared_bank(self, text: torch.Tensor) -> int:
+        if text.dtype != torch.float32 or text.dim() != 2 or text.shape[1] != EMBED_DIM or not text.is_cuda:
+            raise L.WedetectHipError("text bank must be a device float32 [K, 768] tensor")
+        return int(text.shape[0])
+
+    def _grow_text_norm(self, k: int) -> None:
+        if k > self.text_norm.shape[0]:
+            self.text_norm = torch.empty(k, EMBED_DIM, dtype=torch.float32, device=self.dev)
+            self.generation += 1
+
+    def _scores_block(self, kc: int) -> torch.Tensor:
+        """The leading [B, N, kc] block of ``self.scores``, grown to ``kc`` classes first where it is smaller."""
+        if kc > self.max_classes:
+            self._alloc_post(kc)
+        return self.scores.view(-1)[: self.B * self.ntot * kc].view(self.B, self.ntot, kc)
+
+    def _score_bank(self, text: torch.Tensor, normalize: bool, text_counts: Optional[torch.Tensor], sink, *, whole: bool,
+                    sigmoid: bool = True) -> None:
+        """The score step of every mode: validates the bank, picks its path, normalises it, cuts the classes into chunks and hands
+        every chunk to ``sink = (fused, block, fused_chunk, rows_chunk)``:
+          fused(t_split, unscale, kc, c0, seg)   classes [c0, c0 + kc) of a shared bank on the fp16x3 kernel (``_embed_split_valid``,
+                                                 fp16x3, ``want_sim_split(k)`` and a split from ``_split_text``): the sink issues
+                                                 the launch, whose epilogue is what tells the modes apart
+          block(out, kc, c0, counts)             ``out`` [B, N, kc] holds the scores of classes [c0, c0 + kc), written just now by
+                                                 ``wd_similarity_grouped`` (per-image banks; ``counts``: the chunk's own clamped
+                                                 counts, None = all kc) or by the fp32 ``wd_conv_gemm`` (``counts`` None)
+          fused_chunk / rows_chunk               classes per fused launch / per materialised block; None: the whole bank
+        ``whole``: the sink's result IS the score tensor (similarity()): ``self.scores`` grows to the whole bank and ``text_norm``
+        to every shared bank larger than it, up front.  Otherwise ``text_norm`` grows on the split and the normalising paths only
+        and ``self.scores`` to one block of ``rows_chunk`` classes: a growth bumps ``generation``, which stales every GraphedDetect
+        of the tower, so a mode never grows what it does not use."""
+        fused, block, fused_chunk, rows_chunk = sink
+        rows = self.B * self.ntot
         seg = (self.ntot, self.off[1], self.off[2], self.lvl_scale, self.lvl_bias)
-        L.similarity_grouped(self._embed, t, text_counts, out, self.B, self.ntot, k, EMBED_DIM, k, seg, sigmoid=sigmoid)
-        return out
+        self._scores_fold = None
+        if text.dim() == 3 or text_counts is not None:
+            if not isinstance(text, torch.Tensor) or text.dim() != 3 or text.dtype != torch.float32 or text.shape[2] != EMBED_DIM \
+                    or not text.is_cuda or text.device != self._embed.device or text.shape[1] < 1:
+                raise L.WedetectHipError("per-image text banks must be one device float32 [B, k_max, 768] tensor on the tower's device")
+            if text.shape[0] != self.B:
+                raise L.WedetectHipError(f"per-image text banks: {text.shape[0]} banks for a tower of batch {self.B}")
+            self._per_image_seen = True
+            if text_counts is not None:
+                if not isinstance(text_counts, torch.Tensor) or not text_counts.is_cuda or text_counts.device != self._embed.device:
+                    raise L.WedetectHipError("text_counts must be a DEVICE int32 [B] tensor (the kernel reads it; the step has no host read)")
+                if text_counts.dtype != torch.int32 or tuple(text_counts.shape) != (self.B,):
+                    raise L.WedetectHipError(f"text_counts must be int32 of shape [{self.B}], got {text_counts.dtype} {tuple(text_counts.shape)}")
+                text_counts = text_counts.contiguous()
+            k = int(text.shape[1])
+            step = rows_chunk or k
+            for c0 in range(0, k, step):
+                kc = min(step, k - c0)
+                if kc == k:
+                    t, cnt = text.contiguous(), text_counts
+                else:
+                    t = text[:, c0:c0 + kc].contiguous()
+                    cnt = None if text_counts is None else (text_counts - c0).clamp_(0, kc).to(torch.int32)
+                out = self._scores_block(kc)
+                if normalize:
+                    # every row on its own, as in the shared path: row (b, c) gets the bits the 2-D call gives that row
+                    if self.text_norm_pi is None or self.B * kc > self.text_norm_pi.shape[0]:
+                        self.text_norm_pi = torch.empty(self.B * kc, EMBED_DIM, dtype=torch.float32, device=self.dev)
+                        self.generation += 1
+                    tn = self.text_norm_pi[: self.B * kc]
+                    L.l2norm_rows(t.view(self.B * kc, EMBED_DIM), tn)
+                    t = tn.view(self.B, kc, EMBED_DIM)
+                L.similarity_grouped(self._embed, t, cnt, out, self.B, self.ntot, kc, EMBED_DIM, kc, seg, sigmoid=sigmoid)
+                block(out, kc, c0, cnt)
+            return
+        k = self._check_shared_bank(text)
+        t = text.contiguous()
+        if whole:
+            self._scores_block(k)
+            self._grow_text_norm(k)
+        if self._embed_split_valid and self.precision == "fp16x3" and self.want_sim_split(k):
+            self._grow_text_norm(k)
+            ts = self._split_text(t, normalize)
+            if ts is not None:
+                unscale = ts[1] / self.sscale.get("embed", 1.0)
+                step = fused_chunk or k
+                for c0 in range(0, k, step):
+                    fused(ts[0], unscale, min(step, k - c0), c0, seg)
+                return
+        step = rows_chunk or k
+        if normalize:
+            self._grow_text_norm(k)
+            L.l2norm_rows(t, self.text_norm[:k])
+            t = self.text_norm[:k]
+        for c0 in range(0, k, step):
+            kc = min(step, k - c0)
+            out = self._scores_block(kc)
+            L.conv_gemm(self._embed, t[c0:c0 + kc], None, out, batch=1, hin=1, win=rows, cin=EMBED_DIM, lda=EMBED_DIM,
+                        n=kc, ldc=kc, sigmoid=sigmoid, seg=seg)
+            block(out, kc, c0, None)
 
     def _split_text(self, t: torch.Tensor, normalize: bool):
         """fp16 hi/lo groups of the (normalised) text rows, split ONCE per bank: an entry is valid for the same tensor OBJECT
@@ -1453,6 +1511,26 @@ class ImageTower:
     # ------------------------------------------------------------------ post-process
     NMS_MODES = {"vanilla": L.NMS_VANILLA, "torchvision": L.NMS_TORCHVISION, "mmcv": L.NMS_MMCV}
 
+    def _nms_args(self, nms: str, nms_param: Optional[int], nms_device: str, iou_thr: float, agnostic: bool = False):
+        """(nms_mode, mode_param, iou threshold) of wd_nms_gather / wd_nms_gather_labeled for the keywords of the postprocess methods."""
+        mode = self.NMS_MODES[nms]
+        if nms_param is None:
+            nms_param = {L.NMS_VANILLA: 0, L.NMS_TORCHVISION: L.TV_TRICK_MAX_NUMEL[nms_device], L.NMS_MMCV: L.MMCV_SPLIT_THR}[mode]
+        thr = L.nms_threshold(iou_thr, mode, nms_device)
+        if agnostic:
+            if mode != L.NMS_MMCV:
+                raise ValueError("agnostic NMS is the mmcv form's class_agnostic=True")
+            from . import best as BS
+            mode = BS.NMS_MMCV_AGNOSTIC
+        return mode, int(nms_param), thr
+
+    def _result(self, with_embed: bool, **extra) -> Dict[str, torch.Tensor]:
+        res = dict(bboxes=self.out_boxes, scores=self.out_scores, labels=self.out_labels, anchors=self.out_anchors,
+                   count=self.out_count, **extra)
+        if with_embed:
+            res["embeddings"] = self.out_embed
+        return res
+
     def postprocess(self, scores: torch.Tensor, score_thr: float, meta: torch.Tensor, iou_thr: float = 0.7,
                     with_embed: bool = True, nms: str = "vanilla", nms_param: Optional[int] = None,
                     nms_device: str = "cpu") -> Dict[str, torch.Tensor]:
@@ -1470,9 +1548,7 @@ class ImageTower:
         ``score > score_thr`` (score_thr >= 0).  Image b's rows are therefore those of a shared-bank step with its own bank,
         and its labels are < count[b]."""
         B, n, k = scores.shape
-        mode = self.NMS_MODES[nms]
-        if nms_param is None:
-            nms_param = {L.NMS_VANILLA: 0, L.NMS_TORCHVISION: L.TV_TRICK_MAX_NUMEL[nms_device], L.NMS_MMCV: L.MMCV_SPLIT_THR}[mode]
+        mode, mode_param, thr = self._nms_args(nms, nms_param, nms_device, iou_thr)
         L.topk_candidates(scores, B, n * k, float(np.float32(score_thr)), self.nms_pre, self.cand_idx,
                           self.cand_score, self.cand_count, self.topk_ws)
         # a folded step's scores: no embedding tensor to gather from, and the kept rows take the unfolded scores and order
@@ -1482,18 +1558,12 @@ class ImageTower:
         gather = with_embed and folded is None
         if gather and not self._embed_valid:     # scores of the caller's own after a folded step: the rows come from ``embed``
             self._materialise_embed()
-        L.nms_gather(self.cand_idx, self.cand_score, self.cand_count, self.cap, self.boxes, n, k, meta,
-                     L.nms_threshold(iou_thr, mode, nms_device), self.max_out, self._embed if gather else None, EMBED_DIM,
-                     self.out_boxes, self.out_scores, self.out_labels, self.out_anchors, self.out_count,
-                     self.out_embed if gather else None, B, nms_mode=mode, mode_param=int(nms_param),
-                     workspace=self.nms_ws)
+        L.nms_gather(self.cand_idx, self.cand_score, self.cand_count, self.cap, self.boxes, n, k, meta, thr, self.max_out,
+                     self._embed if gather else None, EMBED_DIM, self.out_boxes, self.out_scores, self.out_labels, self.out_anchors,
+                     self.out_count, self.out_embed if gather else None, B, nms_mode=mode, mode_param=mode_param, workspace=self.nms_ws)
         if folded is not None:
             self._kept_rows(folded[0], folded[1], with_embed)
-        res = dict(bboxes=self.out_boxes, scores=self.out_scores, labels=self.out_labels, anchors=self.out_anchors,
-                   count=self.out_count)
-        if with_embed:
-            res["embeddings"] = self.out_embed
-        return res
+        return self._result(with_embed)
 
     # ------------------------------------------------------------------ best class per region (single-label detection)
     def best_scores(self, text: torch.Tensor, normalize: bool, text_counts: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -1515,51 +1585,15 @@ class ImageTower:
             self._best_label = torch.empty(self.B, self.ntot, dtype=torch.int32, device=self.dev)
         key = self._best_key
         key.zero_()
-        seg = (self.ntot, self.off[1], self.off[2], self.lvl_scale, self.lvl_bias)
-        self._scores_fold = None
-        if text.dim() == 3 or text_counts is not None:
-            if not isinstance(text, torch.Tensor) or text.dim() != 3:
-                raise L.WedetectHipError("per-image text banks must be one device float32 [B, k_max, 768] tensor on the tower's device")
-            k = int(text.shape[1])
-            for c0 in range(0, k, BS.ROWS_CHUNK):
-                kc = min(BS.ROWS_CHUNK, k - c0)
-                sub, cnt = text, text_counts
-                if kc != k:
-                    sub = text[:, c0:c0 + kc].contiguous()
-                    cnt = None if text_counts is None else (text_counts - c0).clamp_(0, kc).to(torch.int32)
-                out = self._similarity_per_image(sub, normalize, True, cnt)
-                BS.best_rows(out, self.B, self.ntot, kc, kc, key, c0, cnt)
-            return key
-        k = int(text.shape[0])
-        if text.dtype != torch.float32 or text.dim() != 2 or text.shape[1] != EMBED_DIM or not text.is_cuda:
-            raise L.WedetectHipError("text bank must be a device float32 [K, 768] tensor")
-        t = text.contiguous()
-        if self._embed_split_valid and self.precision == "fp16x3" and self.want_sim_split(k):
-            if k > self.text_norm.shape[0]:
-                self.text_norm = torch.empty(k, EMBED_DIM, dtype=torch.float32, device=self.dev)
-                self.generation += 1
-            ts = self._split_text(t, normalize)
-            if ts is not None:
-                unscale = ts[1] / self.sscale.get("embed", 1.0)
-                for c0 in range(0, k, BS.FUSED_CHUNK):
-                    BS.best_similarity_split(self.embed_s, rows, ts[0], unscale, min(BS.FUSED_CHUNK, k - c0), EMBED_DIM, key, c0, seg=seg,
-                                             range_flag=self.range_flag, t_row=c0)
-                return key
-        kmax = min(k, BS.ROWS_CHUNK)
-        if kmax > self.max_classes:
-            self._alloc_post(kmax)
-        if normalize:
-            if k > self.text_norm.shape[0]:
-                self.text_norm = torch.empty(k, EMBED_DIM, dtype=torch.float32, device=self.dev)
-                self.generation += 1
-            L.l2norm_rows(t, self.text_norm[:k])
-            t = self.text_norm[:k]
-        for c0 in range(0, k, BS.ROWS_CHUNK):
-            kc = min(BS.ROWS_CHUNK, k - c0)
-            out = self.scores.view(-1)[: rows * kc].view(self.B, self.ntot, kc)
-            L.conv_gemm(self._embed, t[c0:c0 + kc], None, out, batch=1, hin=1, win=rows, cin=EMBED_DIM, lda=EMBED_DIM,
-                        n=kc, ldc=kc, sigmoid=True, seg=seg)
-            BS.best_rows(out, self.B, self.ntot, kc, kc, key, c0)
+
+        def fused(t_split, unscale, kc, c0, seg):
+            BS.best_similarity_split(self.embed_s, rows, t_split, unscale, kc, EMBED_DIM, key, c0, seg=seg, range_flag=self.range_flag,
+                                     t_row=c0)
+
+        def block(out, kc, c0, counts):
+            BS.best_rows(out, self.B, self.ntot, kc, kc, key, c0, counts)
+
+        self._score_bank(text, normalize, text_counts, (fused, block, BS.FUSED_CHUNK, BS.ROWS_CHUNK), whole=False)
         return key
 
     def postprocess_best(self, text: torch.Tensor, score_thr: float, meta: torch.Tensor, iou_thr: float = 0.7, with_embed: bool = True,
@@ -1571,26 +1605,15 @@ class ImageTower:
         from . import best as BS
         B, n = self.B, self.ntot
         n_label = int(text.shape[-2])
-        mode = self.NMS_MODES[nms]
-        if nms_param is None:
-            nms_param = {L.NMS_VANILLA: 0, L.NMS_TORCHVISION: L.TV_TRICK_MAX_NUMEL[nms_device], L.NMS_MMCV: L.MMCV_SPLIT_THR}[mode]
-        thr = L.nms_threshold(iou_thr, mode, nms_device)
-        if agnostic:
-            if mode != L.NMS_MMCV:
-                raise ValueError("agnostic NMS is the mmcv form's class_agnostic=True")
-            mode = BS.NMS_MMCV_AGNOSTIC
+        mode, mode_param, thr = self._nms_args(nms, nms_param, nms_device, iou_thr, agnostic)
         BS.best_unpack(self._best_key, B * n, self._best_score, self._best_label)
         L.topk_candidates(self._best_score, B, n, float(np.float32(score_thr)), self.nms_pre, self.cand_idx, self.cand_score,
                           self.cand_count, self.topk_ws)
         BS.nms_gather_labeled(self.cand_idx, self.cand_score, self.cand_count, self.cap, self.boxes, n, self._best_label, n_label, meta,
                               thr, self.max_out, self._embed if with_embed else None, EMBED_DIM, self.out_boxes, self.out_scores,
                               self.out_labels, self.out_anchors, self.out_count, self.out_embed if with_embed else None, B,
-                              nms_mode=mode, mode_param=int(nms_param), workspace=self.nms_ws)
-        res = dict(bboxes=self.out_boxes, scores=self.out_scores, labels=self.out_labels, anchors=self.out_anchors,
-                   count=self.out_count)
-        if with_embed:
-            res["embeddings"] = self.out_embed
-        return res
+                              nms_mode=mode, mode_param=mode_param, workspace=self.nms_ws)
+        return self._result(with_embed)
 
     # ------------------------------------------------------------------ sparse scores (multi-label without the score tensor)
     def sparse_candidates(self, text: torch.Tensor, normalize: bool, score_thr: float, text_counts: Optional[torch.Tensor] = None,
@@ -1623,51 +1646,16 @@ class ImageTower:
         lst, state = self._sparse_list, self._sparse_state
         state.zero_()
         thr = float(np.float32(score_thr))
-        seg = (self.ntot, self.off[1], self.off[2], self.lvl_scale, self.lvl_bias)
-        self._scores_fold = None
-        if text.dim() == 3 or text_counts is not None:
-            if not isinstance(text, torch.Tensor) or text.dim() != 3:
-                raise L.WedetectHipError("per-image text banks must be one device float32 [B, k_max, 768] tensor on the tower's device")
-            k = int(text.shape[1])
-            for c0 in range(0, k, SP.ROWS_CHUNK):
-                kc = min(SP.ROWS_CHUNK, k - c0)
-                sub, cnt = text, text_counts
-                if kc != k:
-                    sub = text[:, c0:c0 + kc].contiguous()
-                    cnt = None if text_counts is None else (text_counts - c0).clamp_(0, kc).to(torch.int32)
-                out = self._similarity_per_image(sub, normalize, True, cnt)
-                SP.sparse_rows(out, self.B, self.ntot, kc, kc, k, thr, lst, cap, state, c0, cnt)
-            return state
-        k = int(text.shape[0])
-        if text.dtype != torch.float32 or text.dim() != 2 or text.shape[1] != EMBED_DIM or not text.is_cuda:
-            raise L.WedetectHipError("text bank must be a device float32 [K, 768] tensor")
-        t = text.contiguous()
-        if self._embed_split_valid and self.precision == "fp16x3" and self.want_sim_split(k):
-            if k > self.text_norm.shape[0]:
-                self.text_norm = torch.empty(k, EMBED_DIM, dtype=torch.float32, device=self.dev)
-                self.generation += 1
-            ts = self._split_text(t, normalize)
-            if ts is not None:
-                unscale = ts[1] / self.sscale.get("embed", 1.0)
-                for c0 in range(0, k, SP.FUSED_CHUNK):
-                    SP.sparse_similarity_split(self.embed_s, rows, ts[0], unscale, min(SP.FUSED_CHUNK, k - c0), EMBED_DIM, self.ntot, k, thr,
-                                               lst, cap, state, cls_offset=c0, seg=seg, range_flag=self.range_flag, t_row=c0)
-                return state
-        kmax = min(k, SP.ROWS_CHUNK)
-        if kmax > self.max_classes:
-            self._alloc_post(kmax)
-        if normalize:
-            if k > self.text_norm.shape[0]:
-                self.text_norm = torch.empty(k, EMBED_DIM, dtype=torch.float32, device=self.dev)
-                self.generation += 1
-            L.l2norm_rows(t, self.text_norm[:k])
-            t = self.text_norm[:k]
-        for c0 in range(0, k, SP.ROWS_CHUNK):
-            kc = min(SP.ROWS_CHUNK, k - c0)
-            out = self.scores.view(-1)[: rows * kc].view(self.B, self.ntot, kc)
-            L.conv_gemm(self._embed, t[c0:c0 + kc], None, out, batch=1, hin=1, win=rows, cin=EMBED_DIM, lda=EMBED_DIM,
-                        n=kc, ldc=kc, sigmoid=True, seg=seg)
-            SP.sparse_rows(out, self.B, self.ntot, kc, kc, k, thr, lst, cap, state, c0)
+        k = int(text.shape[-2])                  # flat index of a candidate = anchor * K + class, K the whole bank's
+
+        def fused(t_split, unscale, kc, c0, seg):
+            SP.sparse_similarity_split(self.embed_s, rows, t_split, unscale, kc, EMBED_DIM, self.ntot, k, thr, lst, cap, state,
+                                       cls_offset=c0, seg=seg, range_flag=self.range_flag, t_row=c0)
+
+        def block(out, kc, c0, counts):
+            SP.sparse_rows(out, self.B, self.ntot, kc, kc, k, thr, lst, cap, state, c0, counts)
+
+        self._score_bank(text, normalize, text_counts, (fused, block, SP.FUSED_CHUNK, SP.ROWS_CHUNK), whole=False)
         return state
 
     def postprocess_sparse(self, text: torch.Tensor, meta: torch.Tensor, iou_thr: float = 0.7, with_embed: bool = True,
@@ -1678,9 +1666,7 @@ class ImageTower:
         -1) and ``sparse_seen`` int32 [B] (candidates seen), device tensors."""
         from . import sparse as SP
         B, n, k = self.B, self.ntot, int(text.shape[-2])
-        mode = self.NMS_MODES[nms]
-        if nms_param is None:
-            nms_param = {L.NMS_VANILLA: 0, L.NMS_TORCHVISION: L.TV_TRICK_MAX_NUMEL[nms_device], L.NMS_MMCV: L.MMCV_SPLIT_THR}[mode]
+        mode, mode_param, thr = self._nms_args(nms, nms_param, nms_device, iou_thr)
         SP.sparse_select(self._sparse_list, self._sparse_list.shape[1], self._sparse_state, B, self.nms_pre, self.cand_idx, self.cand_score,
                          self.cand_count, self._sparse_status)
         # the counters are cleared by the NEXT step's producers, ahead of its post-process: what is returned is a copy made here, which
@@ -1688,15 +1674,10 @@ class ImageTower:
         self._sparse_seen.copy_(self._sparse_state[:, 0])
         if with_embed and not self._embed_valid:
             self._materialise_embed()
-        L.nms_gather(self.cand_idx, self.cand_score, self.cand_count, self.cap, self.boxes, n, k, meta,
-                     L.nms_threshold(iou_thr, mode, nms_device), self.max_out, self._embed if with_embed else None, EMBED_DIM,
-                     self.out_boxes, self.out_scores, self.out_labels, self.out_anchors, self.out_count,
-                     self.out_embed if with_embed else None, B, nms_mode=mode, mode_param=int(nms_param), workspace=self.nms_ws)
-        res = dict(bboxes=self.out_boxes, scores=self.out_scores, labels=self.out_labels, anchors=self.out_anchors,
-                   count=self.out_count, sparse_status=self._sparse_status, sparse_seen=self._sparse_seen)
-        if with_embed:
-            res["embeddings"] = self.out_embed
-        return res
+        L.nms_gather(self.cand_idx, self.cand_score, self.cand_count, self.cap, self.boxes, n, k, meta, thr, self.max_out,
+                     self._embed if with_embed else None, EMBED_DIM, self.out_boxes, self.out_scores, self.out_labels, self.out_anchors,
+                     self.out_count, self.out_embed if with_embed else None, B, nms_mode=mode, mode_param=mode_param, workspace=self.nms_ws)
+        return self._result(with_embed, sparse_status=self._sparse_status, sparse_seen=self._sparse_seen)
 
     def _sparse_wanted(self, text: torch.Tensor, score_thr: float) -> bool:
         """Does this ``sparse_scores=True`` call run sparse?  Not while checked_counts() re-runs an overflowed step, and not for a
@@ -1850,20 +1831,22 @@ class ImageTower:
         # the bank folded into the embedding conv (None: this step runs the unfolded path); folded here, on the caller's stream,
         # ahead of the backbone every later stream of the step waits for
         fold = None if (best_class or sparse) else self._fold_for(text, text_counts, normalize_text)
-        post_best = lambda: self.postprocess_best(text, score_thr, meta, iou_thr, with_embed, nms, nms_param, nms_device, agnostic_nms)
-        post_sparse = lambda: self.postprocess_sparse(text, meta, iou_thr, with_embed, nms, nms_param, nms_device)
+        # the stage of this step: ``score()`` stands behind the head, ``post(what score() returned)`` on the post-process's stream
+        if best_class:
+            score = lambda: self.best_scores(text, normalize=normalize_text, text_counts=text_counts)
+            post = lambda _: self.postprocess_best(text, score_thr, meta, iou_thr, with_embed, nms, nms_param, nms_device, agnostic_nms)
+        elif sparse:
+            score = lambda: self.sparse_candidates(text, normalize_text, score_thr, text_counts=text_counts, sparse_cap=sparse_cap)
+            post = lambda _: self.postprocess_sparse(text, meta, iou_thr, with_embed, nms, nms_param, nms_device)
+        else:
+            score = lambda: self.similarity(text, normalize=normalize_text, text_counts=text_counts, _fold=fold)
+            post = lambda scores: self.postprocess(scores, score_thr, meta, iou_thr, with_embed, nms, nms_param, nms_device)
         if not overlap_post:
             self.wait_post(reads=True)            # a pipelined step, or the caller on the post stream, may still be reading the buffers this one is about to write
             self.features(images_u8, num_classes=num_classes, _fold=fold)
-            if best_class:
-                self.best_scores(text, normalize=normalize_text, text_counts=text_counts)
-                return post_best()
-            if sparse:
-                self.sparse_candidates(text, normalize_text, score_thr, text_counts=text_counts, sparse_cap=sparse_cap)
-                return post_sparse()
-            scores = self.similarity(text, normalize=normalize_text, text_counts=text_counts, _fold=fold)
+            scored = score()
             self._mark_c2(fold)
-            return self.postprocess(scores, score_thr, meta, iou_thr, with_embed, nms, nms_param, nms_device)
+            return post(scored)
         if self.post_stream is None:
             self.post_stream = device_streams(self.dev, "post")[0]
             self._post_ready = torch.cuda.Event()
@@ -1904,14 +1887,7 @@ class ImageTower:
                     self.neck()
                     self.wait_post()
                     self.head(num_classes, fold)
-                if best_class:
-                    scores = None
-                    self.best_scores(text, normalize=normalize_text, text_counts=text_counts)
-                elif sparse:
-                    scores = None
-                    self.sparse_candidates(text, normalize_text, score_thr, text_counts=text_counts, sparse_cap=sparse_cap)
-                else:
-                    scores = self.similarity(text, normalize=normalize_text, text_counts=text_counts, _fold=fold)
+                scored = score()
                 self._mark_c2(fold)
             finally:
                 self._nh_issue = False
@@ -1929,10 +1905,7 @@ class ImageTower:
                     t_.record_stream(nh)
         with torch.cuda.stream(self.post_stream):
             self.post_stream.wait_event(self._post_ready)
-            if sparse:
-                res = post_sparse()
-            else:
-                res = post_best() if best_class else self.postprocess(scores, score_thr, meta, iou_thr, with_embed, nms, nms_param, nms_device)
+            res = post(scored)
             if self._post_done is None:
                 self._post_done = torch.cuda.Event()
             self._post_done.record(self.post_stream)
