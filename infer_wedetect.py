@@ -65,7 +65,14 @@ def parse_args(argv=None):
                              "per-image lists (same results; a list that overflows falls back to the dense step)")
     parser.add_argument("--sparse-cap", default=65536, type=int, help="with --sparse-scores: list entries per image, rounded up to a power of two and to at least the top-k "
                              "capacity of test_cfg.nms_pre (32768 for 30000); up to 2^20")
+    parser.add_argument("--top-names", default=0, type=int,
+                        help="with --best-class: keep the N (1..8) best names of every box; --dump-json then writes them as "
+                             "\"names\": [[name, score], ...] per detection (the drawn label stays the first)")
     args = parser.parse_args(argv)
+    if args.top_names and not args.best_class:
+        parser.exit(2, "infer_wedetect.py: --top-names needs --best-class\n")
+    if not 0 <= args.top_names <= 8:
+        parser.exit(2, "infer_wedetect.py: --top-names takes 0 .. 8\n")
     if args.sparse_scores and args.best_class:
         parser.exit(2, "infer_wedetect.py: --sparse-scores (multi-label) and --best-class (single-label) exclude each other\n")
     if args.sparse_scores and args.tile > 0:
@@ -142,6 +149,8 @@ def main(argv=None, tokenizer=None):
     cfg.work_dir = osp.join("./work_dirs", osp.splitext(osp.basename(args.config))[0])
     if args.best_class:
         cfg.merge_from_dict({"model.best_class": True, "model.agnostic_nms": bool(args.agnostic_nms)})
+    if args.top_names:
+        cfg.merge_from_dict({"model.top_names": int(args.top_names)})
     if args.sparse_scores:
         cfg.merge_from_dict({"model.sparse_scores": True, "model.sparse_cap": int(args.sparse_cap)})
     model = init_detector(cfg, checkpoint=args.checkpoint, device=args.device, palette=["red"], tokenizer=tokenizer,
@@ -169,9 +178,13 @@ def main(argv=None, tokenizer=None):
         out = osp.join(args.output_dir, osp.basename(image_path))
         visualize(out, image_path, pred["bboxes"], labels)
         if args.dump_json:
+            extra = {}
+            if args.top_names:                               # per detection: the names of its list, empty slots (label -1) left out
+                extra["names"] = [[[texts[c][0], float(s)] for c, s in zip(cs, ss) if c >= 0]
+                                  for cs, ss in zip(pred["top_labels"].tolist(), pred["top_scores"].tolist())]
             with open(osp.splitext(out)[0] + ".json", "w") as f:
                 json.dump(dict(image=image_path, bboxes=pred["bboxes"].tolist(), scores=pred["scores"].tolist(),
-                               labels=pred["labels"].tolist(), texts=[t[0] for t in texts]), f, ensure_ascii=False)
+                               labels=pred["labels"].tolist(), texts=[t[0] for t in texts], **extra), f, ensure_ascii=False)
         results.append(pred)
         print(f"[{n + 1}/{len(images)}] {image_path}: {len(pred['scores'])} detections -> {out}", flush=True)
     return results

@@ -204,6 +204,7 @@ __device__ __forceinline__ void p8_best_epilogue(const WdConvGemm& p, unsigned l
 
 constexpr int P8VAR_SPARSE = 32768;     // candidates above a threshold (wd_sparse_similarity_split): p8_sparse_epilogue, at the end of this file
 template <int TM, int TN> __device__ __forceinline__ void p8_sparse_epilogue(const WdConvGemm& p, const P8Retr& rt, float unscale, int mw, int nw, int lane, const f32x16 (&acc)[TM][TN]);
+constexpr int P8VAR_TOPN = 65536; template <int TM, int TN> __device__ __forceinline__ void p8_topn_epilogue(const WdConvGemm& p, const P8Retr& rt, float unscale, int mw, int nw, int lane, const f32x16 (&acc)[TM][TN]);   // the n best classes per region row (wd_topn_similarity_split), at the end of this file
 
 template <int VAR, int ABL = 0, bool PERSIST = false>
 __global__ void __launch_bounds__(512, 2)
@@ -526,6 +527,7 @@ split_gemm_p8_kernel(const WdConvGemm p, const unsigned char* __restrict__ wsp, 
     }
     if constexpr ((VAR & P8VAR_BEST) != 0) { p8_best_epilogue<TM, TN>(p, rt.key, rt.cls_offset, unscale, m0 + group * 128, n0 + wn * 64, lane, acc); continue; }
     if constexpr ((VAR & P8VAR_SPARSE) != 0) { p8_sparse_epilogue<TM, TN>(p, rt, unscale, m0 + group * 128, n0 + wn * 64, lane, acc); continue; }
+    if constexpr ((VAR & P8VAR_TOPN) != 0) { p8_topn_epilogue<TM, TN>(p, rt, unscale, m0 + group * 128, n0 + wn * 64, lane, acc); continue; }
     const EpiVec ev{vec_c, vec_res, vec_bias, unscale};
     const int mw = m0 + group * 128, nw = n0 + wn * 64;
     float* patch = reinterpret_cast<float*>(smem_raw) + wave * 32 * EPI_LDT;
@@ -910,4 +912,89 @@ int wd_launch_p8_sparse(const WdConvGemm& p, const void* t_split, float unscale,
   rt.list = list; rt.list_cap = list_cap; rt.state = state;
   rt.rows_per_img = rows_per_img; rt.n_cls_total = n_cls_total; rt.cls_offset = cls_offset; rt.thr = thr;
   return launch_p8<P8VAR_SPARSE>(p, t_split, unscale, st, nullptr, 0, (p.m + 7) & ~7, (p.n + 7) & ~7, rt);
+}
+
+#include "topn_key.h"
+
+namespace {
+
+// ---- the n best classes per region row on this kernel (wd_topn_similarity_split, include/wedetect_hip_topn.h) ----------------
+// The layout and the scores of p8_best_epilogue: the region row is the LANE (lane & 31), the class the REGISTER, both half-waves hold
+// the same 32 rows of tile i and 32 classes each; every valid element gets the score the materialising epilogue would have stored.
+// Members of P8Retr read here: key [region rows][n_top], cls_offset, list_cap = n_top, scale / bias = the per-row affine (both null: the
+// level affine of p).  A lane reads its row's last slot ONCE (device scope) as the bound, marks which of its 32 keys lie above it
+// (after the first column tiles of a row almost none do, and a wave without one leaves here), then selects the marked keys in
+// descending order — one pass over the 32 registers per key, every index a compile-time constant — and offers the t-th of them to
+// the row at slot t (wd_topn_offer, topn_key.h), reading the bound again in between: the other column tiles of the row raise it.
+// A row with a non-finite accumulator gets NaN score bits in slot 0, as in p8_best_epilogue.
+template <int TM, int TN>
+__device__ __forceinline__ void p8_topn_epilogue(const WdConvGemm& p, const P8Retr& rt, float unscale, int mw, int nw, int lane,
+                                                 const f32x16 (&acc)[TM][TN]) {
+  static_assert(TN * 16 == 32, "one 32-bit mask per (lane, row tile)");
+  if (mw >= p.m || nw >= p.n) return;                              // wave-uniform
+  unsigned long long* key = rt.key;
+  const int n_top = rt.list_cap;
+  const int half = lane >> 5;
+  const int c_lane = nw + 4 * half;                                // class of (j, g, q) = c_lane + 32 j + 8 g + q
+  const unsigned inv0 = 0xFFFFFFFFu - (unsigned)rt.cls_offset - (unsigned)c_lane;
+#pragma unroll
+  for (int i = 0; i < TM; ++i) {
+    if (mw + 32 * i >= p.m) break;                                 // wave-uniform
+    const int m = mw + 32 * i + (lane & 31);
+    const bool row_ok = m < p.m;
+    const int mc = row_ok ? m : p.m - 1;                           // rows past the end: what the padded buffer holds there is not ours to judge
+    EpiRow er = epi_row<true>(p, mc);
+    if (rt.scale) { er.oscale = expf(rt.scale[mc]); er.obias = rt.bias[mc]; }    // wd_topn_affine_score: the same two expressions
+    unsigned long long* slot = key + (size_t)mc * n_top;
+    unsigned long long bound = wd_topn_bound(slot, n_top);
+    unsigned sc[TN * 16];
+    unsigned mask = 0u;
+    bool bad = false;
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int cq = c_lane + 32 * j + 8 * g;
+        if (cq < p.n && row_ok) bad |= wd_any_nonfinite4(acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const unsigned xb = __float_as_uint(p8_score(acc[i][j][4 * g + q], unscale, er));
+          const unsigned long long kq = ((unsigned long long)xb << 32) | (unsigned long long)(inv0 - (unsigned)(32 * j + 8 * g + q));
+          sc[16 * j + 4 * g + q] = xb;
+          mask |= (row_ok && cq + q < p.n && kq > bound) ? (1u << (16 * j + 4 * g + q)) : 0u;
+        }
+      }
+    if (bad) {
+      if (p.range_flag) *p.range_flag = 1u;
+      atomicMax(slot, (0x7FC00000ull << 32) | (unsigned long long)inv0);
+      mask = 0u;
+    }
+    if (__ballot(mask != 0u) == 0ull) continue;                    // wave-uniform: nothing of this group reaches a list
+    unsigned long long prev = ~0ull;
+    for (int t = 0; t < n_top && mask != 0u; ++t) {
+      unsigned long long best = 0ull;
+#pragma unroll
+      for (int e = 0; e < TN * 16; ++e) {
+        const unsigned long long ke = ((unsigned long long)sc[e] << 32) | (unsigned long long)(inv0 - (unsigned)(32 * (e >> 4) + 8 * ((e >> 2) & 3) + (e & 3)));
+        best = (((mask >> e) & 1u) && ke < prev && ke > best) ? ke : best;
+      }
+      if (t > 0) bound = p8_umax64(bound, wd_topn_bound(slot, n_top));
+      if (best <= bound) break;                                    // descending: no later key of this lane is above the bound either
+      wd_topn_offer(slot, n_top, t, best, bound);
+      prev = best;
+    }
+  }
+}
+
+}  // namespace
+
+// wd_topn_similarity_split: the similarity launch with the top-n epilogue (p8_topn_epilogue) in place of the stores; p.c is unused.
+// The caller has checked the sizes (csrc/topn.hip).
+int wd_launch_p8_topn(const WdConvGemm& p, const void* t_split, float unscale, unsigned long long* key, int n_top, int cls_offset,
+                      const float* row_scale, const float* row_bias, hipStream_t st) {
+  if (!p8_similarity_ok(p, t_split) || !p.sigmoid || !key || (reinterpret_cast<uintptr_t>(key) & 7u) || n_top < 1 || n_top > 8) return WD_ERR_UNSUPPORTED;
+  P8Retr rt{};
+  rt.scale = row_scale; rt.bias = row_bias;
+  rt.key = key; rt.cls_offset = cls_offset; rt.list_cap = n_top;
+  return launch_p8<P8VAR_TOPN>(p, t_split, unscale, st, nullptr, 0, (p.m + 7) & ~7, (p.n + 7) & ~7, rt);
 }

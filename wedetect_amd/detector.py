@@ -638,8 +638,15 @@ class YOLOWorldDetector(_DeviceModule):
                  *, mm_neck: bool = False, num_train_classes: int = 80, num_test_classes: int = 80,
                  data_preprocessor=None, backbone=None, neck=None, bbox_head=None, train_cfg=None, init_cfg=None,
                  tokenizer=None, best_class: bool = False, agnostic_nms: bool = False, sparse_scores: bool = False,
-                 sparse_cap: int = 65536):
+                 sparse_cap: int = 65536, top_names: int = 0):
         super().__init__()
+        # the n best names of every detection (also ``model.top_names`` of a config): the best-class step that keeps the
+        # near-winners; ``pred_instances`` gains ``top_labels`` / ``top_scores`` [m, n] (engine.ImageTower.detect)
+        if isinstance(top_names, bool) or not isinstance(top_names, int) or not 0 <= top_names <= 8:
+            raise ValueError(f"top_names must be an int in 0..8, got {top_names!r}")
+        if top_names and not best_class:
+            raise ValueError("top_names needs best_class=True: it is the single-label step with the near-winners kept")
+        self.top_names = top_names
         # sparse scores (also ``model.sparse_scores`` / ``model.sparse_cap`` of a config): the multi-label step whose similarity
         # launch writes candidate lists of ``sparse_cap`` keys per image instead of the [B, N, K] scores (engine.ImageTower.detect)
         self.sparse_scores, self.sparse_cap = bool(sparse_scores), int(sparse_cap)
@@ -867,7 +874,7 @@ class YOLOWorldDetector(_DeviceModule):
                                      iou_thr=self.test_cfg["nms"]["iou_threshold"], with_embed=False,
                                      # mmdet _bbox_post_process -> mmcv.ops.batched_nms(bboxes, scores, labels, cfg.nms)
                                      nms="mmcv", nms_param=int(self.test_cfg["nms"].get("split_thr", 10000)), **self._best_kw(),
-                                     **self._sparse_kw())
+                                     **self._sparse_kw(), **(dict(top_names=self.top_names) if self.top_names else {}))
         res = run()
         recal = (lambda: self._h.recalibrate(tower, x)) if self._h.auto_calibrate else None
         counts = tower.checked_counts(res, run, recal)
@@ -875,6 +882,9 @@ class YOLOWorldDetector(_DeviceModule):
         for j, (i, n) in enumerate(zip(idxs, counts)):
             inst = InstanceData(bboxes=res["bboxes"][j, :n].clone(), scores=res["scores"][j, :n].clone(),
                                 labels=res["labels"][j, :n].to(torch.int64))
+            if self.top_names:
+                inst.top_labels = res["top_labels"][j, :n].to(torch.int64)
+                inst.top_scores = res["top_scores"][j, :n].clone()
             s = samples[i]
             if s is None:
                 s = DetDataSample()
@@ -893,6 +903,7 @@ class YOLOWorldDetector(_DeviceModule):
         replaced by ONE batched launch sequence per batch.  Yields one ``DetDataSample`` per image, in input order, each
         exactly once; ``pred_instances`` holds what ``predict`` fills, as HOST tensors.  ``stats``: a dict that receives
         the stream's counters when it ends."""
+        self._refuse_top_names("predict_stream")
         self._refuse_sparse("predict_stream")
         from .stream import MmdetBackend, predict_stream
         return predict_stream(MmdetBackend(self, pipeline_cfg, rescale), data_infos, batch_size, decode_workers, stats)
@@ -902,7 +913,13 @@ class YOLOWorldDetector(_DeviceModule):
         """The single-label keywords of a tower step; empty for the multi-label default (graph keys stay as they were)."""
         return dict(best_class=True, agnostic_nms=self.agnostic_nms) if self.best_class else {}
 
+    def _refuse_top_names(self, what: str) -> None:
+        if self.top_names:
+            raise NotImplementedError(f"{what} with top_names={self.top_names} is not implemented (its packed result blobs do not "
+                                      "carry the name lists; use predict)")
+
     def _refuse_best(self, what: str) -> None:
+        self._refuse_top_names(what)
         if self.best_class:
             raise NotImplementedError(f"{what} with best_class=True is not implemented (the merges rank (anchor, class) candidates)")
         self._refuse_sparse(what)

@@ -277,6 +277,9 @@ class ImageTower:
         self._best_key: Optional[torch.Tensor] = None         # best-class keys int64 [B * N] (+ unpacked scores / labels), allocated by the first best_scores()
         self._best_score: Optional[torch.Tensor] = None
         self._best_label: Optional[torch.Tensor] = None
+        self._topn_key: Optional[torch.Tensor] = None         # top-n keys int64 [B * N * 8] and the kept lists, allocated by the first topn_scores()
+        self._topn_out_score: Optional[torch.Tensor] = None
+        self._topn_out_label: Optional[torch.Tensor] = None
         # sparse scores (detect(sparse_scores=True), include/wedetect_hip_sparse.h): per-image candidate lists int64 [B, cap],
         # counters int32 [B, 2] and select status int32 [B], allocated by the first sparse_candidates()
         self._sparse_list: Optional[torch.Tensor] = None
@@ -1579,10 +1582,7 @@ class ImageTower:
         from . import best as BS
         self.wait_post()
         rows = self.B * self.ntot
-        if self._best_key is None:
-            self._best_key = torch.empty(rows, dtype=torch.int64, device=self.dev)
-            self._best_score = torch.empty(self.B, self.ntot, dtype=torch.float32, device=self.dev)
-            self._best_label = torch.empty(self.B, self.ntot, dtype=torch.int32, device=self.dev)
+        self._alloc_best()
         key = self._best_key
         key.zero_()
 
@@ -1596,23 +1596,71 @@ class ImageTower:
         self._score_bank(text, normalize, text_counts, (fused, block, BS.FUSED_CHUNK, BS.ROWS_CHUNK), whole=False)
         return key
 
+    def _alloc_best(self) -> None:
+        if self._best_key is None:
+            self._best_key = torch.empty(self.B * self.ntot, dtype=torch.int64, device=self.dev)
+            self._best_score = torch.empty(self.B, self.ntot, dtype=torch.float32, device=self.dev)
+            self._best_label = torch.empty(self.B, self.ntot, dtype=torch.int32, device=self.dev)
+
+    def topn_scores(self, text: torch.Tensor, normalize: bool, n_top: int, text_counts: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The ``n_top`` (1..8) best classes of every region row of the last head as 64-bit keys (include/wedetect_hip_topn.h):
+        int64 [B * N, n_top], score descending, class ascending among equal scores, 0 = empty; slot 0 is the key ``best_scores()``
+        gives, bit for bit.  Issued where ``best_scores()`` is issued, behind ``wait_post()``: it clears and rewrites the keys the
+        previous post-process reads.  The paths are those of ``best_scores()``: ``wd_topn_similarity_split`` for a shared bank of at
+        least SIM_SPLIT_MIN rows on an fp16x3 tower (``self.scores`` is neither used nor grown), otherwise blocks of at most 4096
+        columns in ``self.scores`` and ``wd_topn_rows``.  The buffers are sized for n_top = 8 once, so a change of ``n_top``
+        allocates nothing."""
+        from . import topn as TN
+        n_top = TN.check_n_top(n_top)
+        self.wait_post()
+        rows = self.B * self.ntot
+        self._alloc_best()
+        if self._topn_key is None:
+            self._topn_key = torch.empty(rows * TN.TOPN_MAX, dtype=torch.int64, device=self.dev)
+            self._topn_out_score = torch.empty(self.B * self.max_out * TN.TOPN_MAX, dtype=torch.float32, device=self.dev)
+            self._topn_out_label = torch.empty(self.B * self.max_out * TN.TOPN_MAX, dtype=torch.int32, device=self.dev)
+        key = self._topn_key[: rows * n_top].view(rows, n_top)
+        key.zero_()
+
+        def fused(t_split, unscale, kc, c0, seg):
+            TN.topn_similarity_split(self.embed_s, rows, t_split, unscale, kc, EMBED_DIM, n_top, key, c0, seg=seg,
+                                     range_flag=self.range_flag, t_row=c0)
+
+        def block(out, kc, c0, counts):
+            TN.topn_rows(out, self.B, self.ntot, kc, kc, n_top, key, c0, counts)
+
+        self._score_bank(text, normalize, text_counts, (fused, block, TN.FUSED_CHUNK, TN.ROWS_CHUNK), whole=False)
+        return key
+
     def postprocess_best(self, text: torch.Tensor, score_thr: float, meta: torch.Tensor, iou_thr: float = 0.7, with_embed: bool = True,
                          nms: str = "vanilla", nms_param: Optional[int] = None, nms_device: str = "cpu",
-                         agnostic: bool = False) -> Dict[str, torch.Tensor]:
+                         agnostic: bool = False, top_names: int = 0) -> Dict[str, torch.Tensor]:
         """``postprocess()`` of a ``best_scores()`` step: keys -> (score, label) per anchor -> candidates over N scores per image
         (score desc, anchor asc, <= nms_pre) -> ``wd_nms_gather_labeled`` -> the usual result fields.  ``text`` only names the
-        number of labels.  ``agnostic``: WD_NMS_MMCV_AGNOSTIC in place of the mmcv form."""
+        number of labels.  ``agnostic``: WD_NMS_MMCV_AGNOSTIC in place of the mmcv form.  ``top_names`` = n > 0: the step was scored by
+        ``topn_scores(n_top=n)``; slot 0 of its keys stands for the best-class keys and the result gains ``top_scores`` fp32 /
+        ``top_labels`` int32 [B, max_out, n], the lists of the kept rows ((0, -1) from ``count`` on)."""
         from . import best as BS
         B, n = self.B, self.ntot
         n_label = int(text.shape[-2])
         mode, mode_param, thr = self._nms_args(nms, nms_param, nms_device, iou_thr, agnostic)
-        BS.best_unpack(self._best_key, B * n, self._best_score, self._best_label)
+        if top_names:
+            from . import topn as TN
+            TN.topn_unpack(self._topn_key, B * n, top_names, 0, self._best_score, self._best_label)
+        else:
+            BS.best_unpack(self._best_key, B * n, self._best_score, self._best_label)
         L.topk_candidates(self._best_score, B, n, float(np.float32(score_thr)), self.nms_pre, self.cand_idx, self.cand_score,
                           self.cand_count, self.topk_ws)
         BS.nms_gather_labeled(self.cand_idx, self.cand_score, self.cand_count, self.cap, self.boxes, n, self._best_label, n_label, meta,
                               thr, self.max_out, self._embed if with_embed else None, EMBED_DIM, self.out_boxes, self.out_scores,
                               self.out_labels, self.out_anchors, self.out_count, self.out_embed if with_embed else None, B,
                               nms_mode=mode, mode_param=mode_param, workspace=self.nms_ws)
+        if top_names:
+            m = B * self.max_out * top_names
+            ts = self._topn_out_score[:m].view(B, self.max_out, top_names)
+            tl = self._topn_out_label[:m].view(B, self.max_out, top_names)
+            TN.topn_kept(self._topn_key, top_names, n, self.out_anchors, self.out_count, self.max_out, B, ts, tl)
+            return self._result(with_embed, top_scores=ts, top_labels=tl)
         return self._result(with_embed)
 
     # ------------------------------------------------------------------ sparse scores (multi-label without the score tensor)
@@ -1788,7 +1836,7 @@ class ImageTower:
     def detect(self, images_u8, text, meta, *, normalize_text: bool, score_thr: float, iou_thr: float = 0.7,
                with_embed: bool = False, nms: Optional[str] = None, nms_param: Optional[int] = None, nms_device: str = "cpu",
                overlap_post: bool = False, text_counts: Optional[torch.Tensor] = None, best_class: bool = False,
-               agnostic_nms: bool = False, sparse_scores: bool = False, sparse_cap: int = 65536):
+               agnostic_nms: bool = False, sparse_scores: bool = False, sparse_cap: int = 65536, top_names: int = 0):
         """The whole step.  ``text`` [K, 768] (one bank) or [B, k_max, 768] with ``text_counts`` (one bank per image, see
         similarity(); in line and under ``overlap_post`` alike, same bits).  ``nms`` None picks the library the reference's path of this text handling uses: normalised
         text = BNContrastiveHead of the mmdet path -> "mmcv"; prompts as stored = the Uni scripts -> "torchvision".
@@ -1816,7 +1864,15 @@ class ImageTower:
         (score > score_thr) to per-image lists of ``sparse_cap`` keys instead of the [B, N, K] scores: ``sparse_candidates()`` stands
         where ``similarity()`` stands and ``postprocess_sparse()`` where ``postprocess()`` stands.  Where no list overflows the
         result is the dense step's, bit for bit; the result carries ``sparse_status`` / ``sparse_seen`` and ``checked_counts()``
-        re-runs an overflowed step densely.  Eager, on the unfolded head; exclusive with ``best_class``."""
+        re-runs an overflowed step densely.  Eager, on the unfolded head; exclusive with ``best_class``.
+
+        ``top_names`` = n in 1..8 (with ``best_class``): the best-class step whose score launch keeps the n best (score, class) pairs of
+        every region — ``topn_scores()`` stands where ``best_scores()`` stands.  Every field of the best-class step is unchanged bit
+        for bit; the result gains ``top_scores`` / ``top_labels`` [B, max_out, n], column 0 being ``scores`` / ``labels``.  0: off."""
+        if isinstance(top_names, bool) or not isinstance(top_names, int) or not 0 <= top_names <= 8:
+            raise ValueError(f"top_names must be an int in 0..8, got {top_names!r}")
+        if top_names and not best_class:
+            raise ValueError("top_names needs best_class=True: it is the single-label step with the near-winners kept")
         if sparse_scores and best_class:
             raise ValueError("sparse_scores=True is the multi-label step; best_class=True is the single-label one: choose one")
         sparse = bool(sparse_scores) and self._sparse_wanted(text, score_thr)
@@ -1832,7 +1888,11 @@ class ImageTower:
         # ahead of the backbone every later stream of the step waits for
         fold = None if (best_class or sparse) else self._fold_for(text, text_counts, normalize_text)
         # the stage of this step: ``score()`` stands behind the head, ``post(what score() returned)`` on the post-process's stream
-        if best_class:
+        if best_class and top_names:
+            score = lambda: self.topn_scores(text, normalize_text, top_names, text_counts=text_counts)
+            post = lambda _: self.postprocess_best(text, score_thr, meta, iou_thr, with_embed, nms, nms_param, nms_device, agnostic_nms,
+                                                   top_names=top_names)
+        elif best_class:
             score = lambda: self.best_scores(text, normalize=normalize_text, text_counts=text_counts)
             post = lambda _: self.postprocess_best(text, score_thr, meta, iou_thr, with_embed, nms, nms_param, nms_device, agnostic_nms)
         elif sparse:

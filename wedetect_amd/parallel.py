@@ -388,6 +388,7 @@ _SCORERS: list = []      # small cache of (weakref to the bank, version, precisi
 def clear_scorer_cache() -> None:
     """Drops the cached scorers (and with them the split copies of their banks: 3 GB per 1M x 768 bank)."""
     _SCORERS.clear()
+    _NAMERS.clear()
 
 
 def device_retrieval_scores(embeddings: torch.Tensor, count: torch.Tensor, scales: torch.Tensor, bias: torch.Tensor,
@@ -408,6 +409,108 @@ def device_retrieval_scores(embeddings: torch.Tensor, count: torch.Tensor, scale
     _SCORERS.append((weakref.ref(bank), bank._version, precision, sc))
     del _SCORERS[:-2]
     return sc(embeddings, count, scales, bias, check=check)
+
+
+class RegionNamer:
+    """Names kept regions from a [K, D] text bank: for every region the ``n_top`` (1..8) best classes by
+    sigmoid(<e, t_k> exp(scale) + bias) — the per-region score of retrieval_metric.py:373 BEFORE its max over regions — score
+    descending, class ascending among equal scores (include/wedetect_hip_topn.h).  The [N * R, K] logits are never materialised:
+    the auto-labelling use of the class-agnostic proposals against banks where that tensor cannot exist.
+
+    Structure as :class:`BankScorer`.  ``precision`` "fp16x3" (the default, $WEDETECT_RETRIEVAL_PRECISION): the bank is split ONCE
+    here and scored by ``wd_topn_similarity_split`` with the row affine, in class chunks under the kernel's 2^32-byte limit, under the
+    range guard: the flag is read once per call, and a trip switches the namer for good to the fp32 path and repeats the call.
+    "fp32", banks below 256 rows, dim % 32: ``wd_conv_gemm`` logit blocks of at most 4096 classes, then ``wd_topn_rows`` with the row
+    affine.  One rank, one bank: keys of class shards merge by sorting, which a later change can add."""
+
+    FUSED_MIN = 256              # rows of a bank from which the 256 x 256 kernel is used (engine.ImageTower.SIM_SPLIT_MIN)
+
+    def __init__(self, bank: torch.Tensor, n_top: int, precision: Optional[str] = None):
+        import os
+        from . import topn as TN
+        if precision is None:
+            precision = os.environ.get("WEDETECT_RETRIEVAL_PRECISION", "fp16x3")
+        if precision not in ("fp32", "fp16x3"):
+            raise ValueError("precision must be 'fp32' or 'fp16x3'")
+        if bank.dim() != 2 or bank.dtype != torch.float32 or not bank.is_cuda:
+            raise ValueError("bank must be a device float32 [K, D] tensor")
+        self.n_top = TN.check_n_top(n_top)
+        self.bank = bank.contiguous()
+        self.n_classes, self.dim = int(bank.shape[0]), int(bank.shape[1])
+        self.precision = precision
+        self.overflowed = False
+        self._split = None
+        self.flag = torch.zeros(1, dtype=torch.int32, device=bank.device)
+
+    def _fused_ok(self) -> bool:
+        return self.precision == "fp16x3" and self.dim % 32 == 0 and self.n_classes >= self.FUSED_MIN
+
+    def _launch(self, e, s, b, key) -> bool:
+        from . import lib as L
+        from . import topn as TN
+        rows, d, k, n = e.shape[0], self.dim, self.n_classes, self.n_top
+        if self._fused_ok():
+            if self._split is None:
+                self._split = L.split_weights(self.bank)
+            es = torch.empty(L.LIB.wd_split_weights_bytes(rows, d), dtype=torch.uint8, device=e.device)
+            L.split_weights_scaled(e, es)                       # scale 1, as wd_retrieval_max_split's callers split the region rows
+            row_bytes = (d + 15) // 16 * 16 * 4
+            step = min(TN.FUSED_CHUNK, (((1 << 32) - 1) // row_bytes - 8) // 8 * 8)
+            for c0 in range(0, k, step):
+                TN.topn_similarity_split(es, rows, self._split[0], self._split[1], min(step, k - c0), d, n, key, c0, row_scale=s, row_bias=b,
+                                         range_flag=self.flag, t_row=c0)
+            return True
+        block = torch.empty(rows, min(TN.ROWS_CHUNK, k), dtype=torch.float32, device=e.device)
+        for c0 in range(0, k, TN.ROWS_CHUNK):
+            kc = min(TN.ROWS_CHUNK, k - c0)
+            L.conv_gemm(e, self.bank[c0:c0 + kc], None, block, batch=1, hin=1, win=rows, cin=d, lda=d, n=kc, ldc=kc)
+            TN.topn_rows(block, 1, rows, kc, kc, n, key, c0, row_scale=s, row_bias=b)
+        return False
+
+    def __call__(self, embeddings, count, scales, bias):
+        """``embeddings`` [N, R, D], ``count`` [N], ``scales`` / ``bias`` [N, R] -> (scores [N, R, n_top] fp32, labels [N, R, n_top]
+        int32); regions r >= count[i] and slots beyond the bank come out empty: (0, -1)."""
+        import warnings
+        from . import topn as TN
+        n_img, r, d = embeddings.shape
+        if d != self.dim:
+            raise ValueError(f"embeddings of dim {d} against a bank of dim {self.dim}")
+        dev, n = embeddings.device, self.n_top
+        e = embeddings.contiguous().view(n_img * r, d)
+        s, b = scales.contiguous().view(-1), bias.contiguous().view(-1)
+        c = count.to(torch.int32).contiguous()
+        key = torch.zeros(n_img * r, n, dtype=torch.int64, device=dev)
+        if self._launch(e, s, b, key) and bool(int(self.flag.item())):
+            warnings.warn("wedetect_amd: a region embedding left the fp16 range in the fp16x3 top-n kernel; this namer now runs the "
+                          "fp32 path")
+            self.precision, self.overflowed = "fp32", True
+            self.flag.zero_()
+            key.zero_()
+            self._launch(e, s, b, key)
+        # every region is its own "kept row": wd_topn_kept lays the lists out as [N][R][n] and empties the rows from count on
+        rows_of = torch.arange(r, dtype=torch.int32, device=dev).repeat(n_img, 1)
+        scores = torch.empty(n_img, r, n, dtype=torch.float32, device=dev)
+        labels = torch.empty(n_img, r, n, dtype=torch.int32, device=dev)
+        TN.topn_kept(key, n, r, rows_of, c, r, n_img, scores, labels)
+        return scores, labels
+
+
+_NAMERS: list = []       # (weakref to the bank, version, n_top, precision, RegionNamer), as _SCORERS
+
+
+def device_region_names(embeddings: torch.Tensor, count: torch.Tensor, scales: torch.Tensor, bias: torch.Tensor, bank: torch.Tensor,
+                        n_top: int, precision: Optional[str] = None):
+    """:class:`RegionNamer` with the namer (and the bank's split form) cached per bank tensor, as
+    :func:`device_retrieval_scores` caches its scorer: by weak reference and version counter, the last two banks."""
+    import weakref
+    _NAMERS[:] = [ent for ent in _NAMERS if ent[0]() is not None]
+    for ref, ver, nt, prec, nm in _NAMERS:
+        if ref() is bank and ver == bank._version and nt == n_top and prec == precision:
+            return nm(embeddings, count, scales, bias)
+    nm = RegionNamer(bank, n_top, precision)
+    _NAMERS.append((weakref.ref(bank), bank._version, n_top, precision, nm))
+    del _NAMERS[:-2]
+    return nm(embeddings, count, scales, bias)
 
 
 def class_sharded_retrieval(embeddings: torch.Tensor, count: torch.Tensor, scales: torch.Tensor, bias: torch.Tensor,
