@@ -68,7 +68,14 @@ def parse_args(argv=None):
     parser.add_argument("--top-names", default=0, type=int,
                         help="with --best-class: keep the N (1..8) best names of every box; --dump-json then writes them as "
                              "\"names\": [[name, score], ...] per detection (the drawn label stays the first)")
+    parser.add_argument("--prompt-groups", action="store_true",
+                        help="score every class as the best of several names: inside --text, '/' separates the names of one class "
+                             "(\"person/man/woman,dog/puppy\"); --text-bank then holds one row per NAME plus the blank class")
     args = parser.parse_args(argv)
+    if args.prompt_groups and (args.best_class or args.sparse_scores or args.top_names):
+        parser.exit(2, "infer_wedetect.py: --prompt-groups excludes --best-class, --sparse-scores and --top-names\n")
+    if args.prompt_groups and args.tile > 0:
+        parser.exit(2, "infer_wedetect.py: --prompt-groups is not implemented for tiled inference (--tile)\n")
     if args.top_names and not args.best_class:
         parser.exit(2, "infer_wedetect.py: --top-names needs --best-class\n")
     if not 0 <= args.top_names <= 8:
@@ -84,13 +91,17 @@ def parse_args(argv=None):
     return args
 
 
-def read_texts(spec: str):
-    """infer_wedetect.py:162-167."""
+def read_texts(spec: str, groups: bool = False):
+    """infer_wedetect.py:162-167.  ``groups`` (--prompt-groups): '/' separates the names of one class."""
     if spec.endswith(".txt"):
         with open(spec) as f:
             lines = f.readlines()
-        return [[t.rstrip("\r\n")] for t in lines] + [[" "]]
-    return [[t.strip()] for t in spec.split(",")] + [[" "]]
+        items = [t.rstrip("\r\n") for t in lines]
+    else:
+        items = [t.strip() for t in spec.split(",")]
+    if groups:
+        return [[n.strip() for n in t.split("/") if n.strip()] or [t] for t in items] + [[" "]]
+    return [[t] for t in items] + [[" "]]
 
 
 def list_images(path: str):
@@ -153,17 +164,20 @@ def main(argv=None, tokenizer=None):
         cfg.merge_from_dict({"model.top_names": int(args.top_names)})
     if args.sparse_scores:
         cfg.merge_from_dict({"model.sparse_scores": True, "model.sparse_cap": int(args.sparse_cap)})
+    if args.prompt_groups:
+        cfg.merge_from_dict({"model.prompt_groups": True})
     model = init_detector(cfg, checkpoint=args.checkpoint, device=args.device, palette=["red"], tokenizer=tokenizer,
                           precision=args.precision)
     test_pipeline = Compose(cfg.test_pipeline)
-    texts = read_texts(args.text)
+    texts = read_texts(args.text, args.prompt_groups)
     if not osp.exists(args.output_dir):
         os.makedirs(args.output_dir)
     images = list_images(args.image)
     if args.text_bank:
         bank = load_bank(args.text_bank)
-        if bank.shape != (len(texts), 768):
-            raise SystemExit(f"--text-bank holds {tuple(bank.shape)}, expected ({len(texts)}, 768): one row per prompt "
+        n_rows = sum(len(t) for t in texts) if args.prompt_groups else len(texts)
+        if bank.shape != (n_rows, 768):
+            raise SystemExit(f"--text-bank holds {tuple(bank.shape)}, expected ({n_rows}, 768): one row per prompt "
                              f"plus the blank class")
         model.set_text_embeddings(bank, texts)
     else:

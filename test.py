@@ -65,7 +65,15 @@ def parse_args(argv=None):
                              "per-image lists (same results; a list that overflows falls back to the dense step)")
     parser.add_argument("--sparse-cap", default=65536, type=int, help="with --sparse-scores: list entries per image, rounded up to a power of two and to at least the top-k "
                              "capacity of test_cfg.nms_pre (32768 for 30000); up to 2^20")
+    parser.add_argument("--prompt-groups", action="store_true",
+                        help="score every class as the best of ALL the prompts its entry of the class-text file lists (synonyms), "
+                             "not of the first one; --text-bank then holds (P, 768): one row per prompt, class after class")
     args = parser.parse_args(argv)
+    if args.prompt_groups and (args.best_class or args.sparse_scores):
+        parser.exit(2, "test.py: --prompt-groups excludes --best-class and --sparse-scores\n")
+    if args.prompt_groups and (args.aug_test or args.loader == "stream"):
+        parser.exit(2, "test.py: --prompt-groups runs with --loader serial and without --aug-test (the streamed loader and the "
+                       "view merge are not built for it)\n")
     if args.sparse_scores and args.best_class:
         parser.exit(2, "test.py: --sparse-scores (multi-label) and --best-class (single-label) exclude each other\n")
     if args.sparse_scores and (args.aug_test or args.loader == "stream"):
@@ -184,6 +192,8 @@ def main(argv=None):
         cfg.merge_from_dict({"model.best_class": True, "model.agnostic_nms": bool(args.agnostic_nms)})
     if args.sparse_scores:
         cfg.merge_from_dict({"model.sparse_scores": True, "model.sparse_cap": int(args.sparse_cap)})
+    if args.prompt_groups:
+        cfg.merge_from_dict({"model.prompt_groups": True})
     if args.work_dir is not None:
         cfg.work_dir = args.work_dir
     elif cfg.get("work_dir", None) is None:
@@ -205,9 +215,16 @@ def main(argv=None):
     model = init_detector(cfg, checkpoint=args.checkpoint, device=device, precision=args.precision)
     if args.text_bank:
         bank = load_bank(args.text_bank)
-        if tuple(bank.shape) != (len(texts), 768):
+        if args.prompt_groups:
+            n_prompts = sum(len(t) for t in texts)
+            if tuple(bank.shape) != (n_prompts, 768):
+                raise SystemExit(f"--text-bank holds {tuple(bank.shape)}, expected ({n_prompts}, 768) with --prompt-groups: one row "
+                                 f"per prompt of the {len(texts)} classes, class after class")
+        elif tuple(bank.shape) != (len(texts), 768):
             raise SystemExit(f"--text-bank holds {tuple(bank.shape)}, expected ({len(texts)}, 768): one row per class text")
         model.set_text_embeddings(bank.to(device), texts)
+    elif args.prompt_groups:
+        model.reparameterize(texts)                           # every prompt of every class: the samples' first captions find this bank
     batch_size = int(cfg.test_dataloader.get("batch_size", 1))
     shard = parallel.shard_range(len(dataset), world, rank)
     t0 = time.time()

@@ -119,13 +119,13 @@ constexpr int P8VAR_RETR = 4096;
 constexpr int P8VAR_DIRECT = 8192;      // with SVAR_CSPLIT: the direct (no LDS transpose) hi/lo epilogue; GELU / no activation only
 // One argument block for the epilogues that do not store the product; a launch fills its own members.  RETR: scale, bias [region rows]
 // (logit scale applied as exp(scale)); count [images]: valid rows of an image (the first count[i] of its rows_per_img); out [images][ldo]
-// zero-filled: max over an image's valid rows of sigmoid(<e, t> exp(scale) + bias).  BEST / SPARSE: see their epilogues below.
+// zero-filled: max over an image's valid rows of sigmoid(<e, t> exp(scale) + bias).  BEST / SPARSE / GROUP: see their epilogues below.
 struct P8Retr {
-  const float *scale, *bias;
+  union { const float* scale; const int* group_of; }; union { const float* bias; const int* bin_first; };
   union { const int* count; int* state; };
   union { float* out; unsigned long long* key; unsigned long long* list; };
   int rows_per_img; union { int ldo; int cls_offset; };
-  int n_cls_total, list_cap; float thr;
+  union { int n_cls_total; int ldg; }; union { int list_cap; int n_groups; }; float thr;
 };
 
 template <int TM, int TN>
@@ -204,7 +204,7 @@ __device__ __forceinline__ void p8_best_epilogue(const WdConvGemm& p, unsigned l
 
 constexpr int P8VAR_SPARSE = 32768;     // candidates above a threshold (wd_sparse_similarity_split): p8_sparse_epilogue, at the end of this file
 template <int TM, int TN> __device__ __forceinline__ void p8_sparse_epilogue(const WdConvGemm& p, const P8Retr& rt, float unscale, int mw, int nw, int lane, const f32x16 (&acc)[TM][TN]);
-constexpr int P8VAR_TOPN = 65536; template <int TM, int TN> __device__ __forceinline__ void p8_topn_epilogue(const WdConvGemm& p, const P8Retr& rt, float unscale, int mw, int nw, int lane, const f32x16 (&acc)[TM][TN]);   // the n best classes per region row (wd_topn_similarity_split), at the end of this file
+constexpr int P8VAR_TOPN = 65536; template <int TM, int TN> __device__ __forceinline__ void p8_topn_epilogue(const WdConvGemm& p, const P8Retr& rt, float unscale, int mw, int nw, int lane, const f32x16 (&acc)[TM][TN]); constexpr int P8VAR_GROUP = 131072; template <int TM, int TN> __device__ __forceinline__ void p8_group_epilogue(const WdConvGemm& p, const P8Retr& rt, float unscale, int mw, int nw, int lane, const f32x16 (&acc)[TM][TN], float* patch);   // the n best classes per region row (wd_topn_similarity_split), at the end of this file; P8VAR_GROUP: the best prompt of every class (wd_group_similarity_split), at the end of this file
 
 template <int VAR, int ABL = 0, bool PERSIST = false>
 __global__ void __launch_bounds__(512, 2)
@@ -527,7 +527,7 @@ split_gemm_p8_kernel(const WdConvGemm p, const unsigned char* __restrict__ wsp, 
     }
     if constexpr ((VAR & P8VAR_BEST) != 0) { p8_best_epilogue<TM, TN>(p, rt.key, rt.cls_offset, unscale, m0 + group * 128, n0 + wn * 64, lane, acc); continue; }
     if constexpr ((VAR & P8VAR_SPARSE) != 0) { p8_sparse_epilogue<TM, TN>(p, rt, unscale, m0 + group * 128, n0 + wn * 64, lane, acc); continue; }
-    if constexpr ((VAR & P8VAR_TOPN) != 0) { p8_topn_epilogue<TM, TN>(p, rt, unscale, m0 + group * 128, n0 + wn * 64, lane, acc); continue; }
+    if constexpr ((VAR & P8VAR_TOPN) != 0) { p8_topn_epilogue<TM, TN>(p, rt, unscale, m0 + group * 128, n0 + wn * 64, lane, acc); continue; } if constexpr ((VAR & P8VAR_GROUP) != 0) { p8_group_epilogue<TM, TN>(p, rt, unscale, m0 + group * 128, n0 + wn * 64, lane, acc, reinterpret_cast<float*>(smem_raw) + wave * 32 * EPI_LDT); continue; }
     const EpiVec ev{vec_c, vec_res, vec_bias, unscale};
     const int mw = m0 + group * 128, nw = n0 + wn * 64;
     float* patch = reinterpret_cast<float*>(smem_raw) + wave * 32 * EPI_LDT;
@@ -717,7 +717,7 @@ int wd_launch_p8_retrieval(const void* t_split, int n_cls, const void* e_split, 
   p.m = n_cls; p.n = n_rows; p.k = dim; p.ldc = ldo;
   p.out_scale = 1.0f;
   p.range_flag = range_flag;
-  return launch_p8_retr(p, e_split, unscale, P8Retr{scale, bias, {count}, {out}, rows_per_img, {ldo}}, st);
+  return launch_p8_retr(p, e_split, unscale, P8Retr{{scale}, {bias}, {count}, {out}, rows_per_img, {ldo}}, st);
 }
 
 // wd_similarity_split on the 256 x 256 kernel (round 6; yolo_world_head.py:90-108, generate_proposal.py:1129-1131): region rows
@@ -743,7 +743,9 @@ namespace {
 static_assert(sizeof(P8Retr) == 56 && offsetof(P8Retr, scale) == 0 && offsetof(P8Retr, bias) == 8 && offsetof(P8Retr, count) == 16 &&
               offsetof(P8Retr, state) == 16 && offsetof(P8Retr, out) == 24 && offsetof(P8Retr, key) == 24 && offsetof(P8Retr, list) == 24 &&
               offsetof(P8Retr, rows_per_img) == 32 && offsetof(P8Retr, ldo) == 36 && offsetof(P8Retr, cls_offset) == 36 &&
-              offsetof(P8Retr, n_cls_total) == 40 && offsetof(P8Retr, list_cap) == 44 && offsetof(P8Retr, thr) == 48, "P8Retr layout");
+              offsetof(P8Retr, n_cls_total) == 40 && offsetof(P8Retr, list_cap) == 44 && offsetof(P8Retr, thr) == 48 &&
+              offsetof(P8Retr, group_of) == 0 && offsetof(P8Retr, bin_first) == 8 && offsetof(P8Retr, ldg) == 40 &&
+              offsetof(P8Retr, n_groups) == 44, "P8Retr layout");
 
 // The score of accumulator element v of a row, for the two epilogues below: the expressions of the materialising epilogue
 // (epi_quad<WD_ACT_NONE, true>), so the bits it would have stored.
@@ -997,4 +999,122 @@ int wd_launch_p8_topn(const WdConvGemm& p, const void* t_split, float unscale, u
   rt.scale = row_scale; rt.bias = row_bias;
   rt.key = key; rt.cls_offset = cls_offset; rt.list_cap = n_top;
   return launch_p8<P8VAR_TOPN>(p, t_split, unscale, st, nullptr, 0, (p.m + 7) & ~7, (p.n + 7) & ~7, rt);
+}
+
+namespace {
+
+// ---- the best prompt of every class on this kernel (wd_group_similarity_split, include/wedetect_hip_groups.h) -----------------
+// The layout and the scores of p8_best_epilogue: the region row is the LANE (lane & 31), the bank row the REGISTER, and the 32 bank
+// rows nw + 32 j .. + 31 of accumulator tile (i, j) are ONE BIN of the packing (cls_offset and nw are multiples of 32), split
+// between lane L and lane L ^ 32.  Which rows of a bin belong to which class depends on the column only: wave-uniform.
+// Members of P8Retr read here: group_of, bin_first (the whole tables), cls_offset, out [region rows][ldg], n_groups.
+// Per bin (j): the wave reads the bin's classes [g0, g0 + ng) and its 32 group_of words (uniform loads).  The (row, class) pairs
+// of a 32-row tile are dealt in passes of rp = min(32, 64 / ng) rows x ng classes: lane = (row r0 of the pass, class k = lane % ng),
+// the SAME class in every pass, so a lane counts the columns in front of class g0 + k and those of it, (start, ln), once per bin;
+// the longest class of the bin bounds the read loop.
+// Per (i, j): every lane writes its 16 SCORES (p8_score per element: the materialised bits) to the wave's 32 x 36-float patch —
+// the patch of the materialising epilogue, transposed the same way — then, per pass, a lane reads the columns of its class in its
+// row from the patch, four independent reads at a time (a shorter class re-reads its last column: max is idempotent), and stores
+// the maximum at out[row][g0 + k].  Consecutive lanes store consecutive classes of a row: row segments of ng floats, every element
+// written exactly once, no atomics, nothing cleared.  (A first form dealt the pairs 64 per pass with the class changing per
+// pass — a lane exchange and a serial read loop in every pass: 3.53 ms, this form 3.02 ms, against 2.39 ms of the materialising launch on the LVIS
+// plan, profiles/prompt_groups.txt.)  A non-finite accumulator of (row, bin) raises the range flag and turns the row's 32 patch
+// entries into NaN, so every class of the bin gets NaN in that row (fmaxf(NaN, NaN) = NaN).
+// No register is indexed dynamically: i, j, g, q are unrolled, the pass loop touches the patch only.
+template <int TM, int TN>
+__device__ __forceinline__ void p8_group_epilogue(const WdConvGemm& p, const P8Retr& rt, float unscale, int mw, int nw, int lane,
+                                                  const f32x16 (&acc)[TM][TN], float* patch) {
+  if (mw >= p.m || nw >= p.n) return;                              // wave-uniform
+  const int half = lane >> 5, l31 = lane & 31;
+  const float qnan = __uint_as_float(0x7FC00000u);
+#pragma unroll
+  for (int j = 0; j < TN; ++j) {
+    const int c0 = nw + 32 * j;                                    // first bank row of the bin, in this launch
+    if (c0 >= p.n) break;                                          // wave-uniform (p.n is a multiple of 32: a bin is in or out)
+    const int abin = (rt.cls_offset + c0) >> 5;
+    const int g0 = rt.bin_first[abin];
+    int ng = rt.bin_first[abin + 1] - g0;
+    ng = (g0 < 0 || ng < 0) ? 0 : (ng > 32 ? 32 : ng);             // a table that is no plan's: nothing is stored
+    ng = __builtin_amdgcn_readfirstlane(ng);
+    if (ng == 0) continue;
+    // the (row, class) pairs of a pass: rp = min(32, 64 / ng) rows of ng classes; lane = (row r0 of the pass, class k), the same
+    // class in every pass, so its column range is found once per bin
+    const int magic = (65536 + ng - 1) / ng;                       // x / ng = (x * magic) >> 16 for x < 1024, ng <= 32
+    const int rp = ng <= 2 ? 32 : (64 * magic) >> 16;
+    const int r0 = (lane * magic) >> 16;
+    const int k = lane - r0 * ng;
+    const int* __restrict__ go = rt.group_of + rt.cls_offset + c0;
+    const int mine = g0 + k;
+    int start = 0, end = 0, run = 0, maxl = 1, prev = 0;
+#pragma unroll
+    for (int c = 0; c < 32; ++c) {
+      const int gc = go[c];
+      start += gc < mine ? 1 : 0;
+      end += gc <= mine ? 1 : 0;
+      run = (c > 0 && gc == prev) ? run + 1 : 1;
+      maxl = run > maxl ? run : maxl;
+      prev = gc;
+    }
+    maxl = __builtin_amdgcn_readfirstlane(maxl);
+    const int ln = end - start, last = ln > 0 ? ln - 1 : 0;        // columns of class g0 + k: [start, start + ln); ln = 0: a table that is no plan's
+    const bool lane_ok = r0 < rp && ln > 0 && g0 + k < rt.n_groups;
+    const int o1 = last < 1 ? last : 1, o2 = last < 2 ? last : 2, o3 = last < 3 ? last : 3;
+    const int lane_off = (r0 < 32 ? r0 : 0) * EPI_LDT + start;     // start + last <= 31; ln = 0: start <= 32, inside the 36-float pitch
+    float* const outk = rt.out + g0 + k;
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+      const int m_first = mw + 32 * i;
+      if (m_first >= p.m) break;                                   // wave-uniform
+      const int m = m_first + l31;
+      const bool row_ok = m < p.m;
+      const EpiRow er = epi_row<true>(p, row_ok ? m : p.m - 1);     // rows past the end: what the padded buffer holds there is not ours to judge
+      bool bad = false;
+#pragma unroll
+      for (int g = 0; g < 4; ++g)
+        bad |= wd_any_nonfinite4(acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]);
+      bad = bad && row_ok;
+      bad = bad || (__shfl_xor((int)bad, 32, 64) != 0);            // the other 16 bank rows of the bin
+      if (bad && p.range_flag) *p.range_flag = 1u;
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        f32x4 s;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) s[q] = bad ? qnan : p8_score(acc[i][j][4 * g + q], unscale, er);
+        *reinterpret_cast<f32x4*>(patch + l31 * EPI_LDT + 8 * g + 4 * half) = s;
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      for (int rb = 0; rb < 32; rb += rp) {
+        const int r = rb + r0;                                     // row of the tile
+        const float* src = patch + (r < 32 ? rb : 0) * EPI_LDT + lane_off;
+        // four independent reads (a class of fewer columns re-reads its last one: max is idempotent), then the rare long classes
+        const float v0 = src[0], v1 = src[o1], v2 = src[o2], v3 = src[o3];
+        float v = fmaxf(fmaxf(v0, v1), fmaxf(v2, v3));
+        for (int t = 4; t < maxl; t += 4) {
+          const float w0 = src[t < last ? t : last], w1 = src[t + 1 < last ? t + 1 : last], w2 = src[t + 2 < last ? t + 2 : last],
+                      w3 = src[t + 3 < last ? t + 3 : last];
+          v = fmaxf(v, fmaxf(fmaxf(w0, w1), fmaxf(w2, w3)));
+        }
+        const int mm = m_first + r;
+        if (lane_ok && r < 32 && mm < p.m) outk[(size_t)mm * rt.ldg] = v;
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+  }
+}
+
+}  // namespace
+
+// wd_group_similarity_split: the similarity launch with the class-max epilogue (p8_group_epilogue) in place of the stores; p.c is
+// unused.  The caller has checked the sizes and the alignment of the tables (csrc/groups.hip); p.n % 32 == 0.
+int wd_launch_p8_group(const WdConvGemm& p, const void* t_split, float unscale, const int* group_of, const int* bin_first, int cls_offset,
+                       float* out, int ldo, int n_groups, hipStream_t st) {
+  if (!p8_similarity_ok(p, t_split) || !p.sigmoid || !group_of || !bin_first || !out || (p.n & 31) || (cls_offset & 31)) return WD_ERR_UNSUPPORTED;
+  P8Retr rt{};
+  rt.group_of = group_of; rt.bin_first = bin_first;
+  rt.out = out; rt.cls_offset = cls_offset; rt.ldg = ldo; rt.n_groups = n_groups;
+  return launch_p8<P8VAR_GROUP>(p, t_split, unscale, st, nullptr, 0, (p.m + 7) & ~7, p.n, rt);
 }

@@ -204,9 +204,9 @@ class _TowerHolder:
         step, tests/test_gpu_detector.py).  A graph belongs to one (tower, arithmetic mode, bank size, thresholds); the
         range guard's switch to fp32 therefore captures anew."""
         self.calibrate_first(tower, images_u8)
-        if kw.get("best_class") or kw.get("sparse_scores"):
-            # single-label and sparse-score steps run eagerly on the unfolded head (the best_scores / sparse_candidates sinks of
-            # engine.ImageTower._score_bank): no graph, no fold
+        if kw.get("best_class") or kw.get("sparse_scores") or kw.get("prompt_groups") is not None:
+            # single-label, sparse-score and prompt-group steps run eagerly on the unfolded head (the best_scores / sparse_candidates /
+            # group_scores sinks of engine.ImageTower._score_bank): no graph, no fold
             return tower.detect(images_u8, text, meta, text_counts=text_counts, **kw)
         if text.dim() == 3 or text_counts is not None:
             # one bank per image ([B, k_max, 768] + device counts): always the eager step, never captured — a graph would
@@ -638,8 +638,15 @@ class YOLOWorldDetector(_DeviceModule):
                  *, mm_neck: bool = False, num_train_classes: int = 80, num_test_classes: int = 80,
                  data_preprocessor=None, backbone=None, neck=None, bbox_head=None, train_cfg=None, init_cfg=None,
                  tokenizer=None, best_class: bool = False, agnostic_nms: bool = False, sparse_scores: bool = False,
-                 sparse_cap: int = 65536, top_names: int = 0):
+                 sparse_cap: int = 65536, top_names: int = 0, prompt_groups: bool = False):
         super().__init__()
+        # prompt groups (also ``model.prompt_groups`` of a config): every class is scored as the best of ALL its prompts — the
+        # synonym lists of the class-text files — instead of its first caption (wedetect_amd/groups.py, engine.ImageTower.detect)
+        self.prompt_groups = bool(prompt_groups)
+        if self.prompt_groups and (best_class or sparse_scores or top_names):
+            raise ValueError("prompt_groups=True is a multi-label dense step of its own: it excludes best_class, sparse_scores and top_names")
+        self._plans: Dict[Tuple[str, ...], object] = {}      # first captions -> groups.PromptGroups of that bank (prompt_groups only)
+        self._plan_cur = None                                # the plan of ``text_feats``
         # the n best names of every detection (also ``model.top_names`` of a config): the best-class step that keeps the
         # near-winners; ``pred_instances`` gains ``top_labels`` / ``top_scores`` [m, n] (engine.ImageTower.detect)
         if isinstance(top_names, bool) or not isinstance(top_names, int) or not 0 <= top_names <= 8:
@@ -763,6 +770,17 @@ class YOLOWorldDetector(_DeviceModule):
             feats = feats[0]
         if feats.dim() != 2 or feats.shape[1] != EMBED_DIM:
             raise ValueError("text embeddings must be [K, 768]")
+        if self.prompt_groups:
+            # the bank holds one row per PROMPT, class after class; the tower sees it padded to bins of 32 rows (groups.PromptGroups)
+            if texts is None:
+                raise ValueError("prompt_groups=True: set_text_embeddings needs the class lists (texts) the [P, 768] rows belong to")
+            from .groups import PromptGroups
+            plan = PromptGroups.from_texts(texts)
+            if feats.shape[0] != plan.P:
+                raise ValueError(f"prompt_groups=True: text embeddings must be ({plan.P}, {EMBED_DIM}), one row per prompt of the "
+                                 f"{plan.G} classes, got {tuple(feats.shape)}")
+            feats = plan.pad_bank(feats.detach().to(torch.float32))
+            self._plans[_flat_texts(texts)] = self._plan_cur = plan
         self.text_feats = feats.detach().to(torch.float32)
         self.texts = texts
         if texts is not None:
@@ -779,6 +797,8 @@ class YOLOWorldDetector(_DeviceModule):
     def reparameterize(self, texts: List[List[str]]) -> None:
         """yolo_world.py:58-61: ``self.texts = texts; self.text_feats = self.backbone.forward_text(texts)``."""
         flat = _flat_texts(texts)
+        if self.prompt_groups:                               # ALL prompts of every class, class after class
+            flat = tuple(p for t in texts for p in ([t] if isinstance(t, str) else t))
         self.set_text_embeddings(self._encode(flat), texts)
 
     def _bank_for(self, sample) -> torch.Tensor:
@@ -795,8 +815,21 @@ class YOLOWorldDetector(_DeviceModule):
         if bank is None:
             if len(self._banks) > 64:
                 self._banks.clear()
+                self._plans.clear()
+            if self.prompt_groups:
+                # a class list seen for the first time in a data sample: grouped as it is given (LoadText leaves first captions
+                # only — classes of one prompt; banks with synonyms come through reparameterize / set_text_embeddings)
+                from .groups import PromptGroups
+                plan = self._plans[flat] = PromptGroups.from_texts(texts)
+                bank = self._banks[flat] = plan.pad_bank(self._encode(tuple(plan.flat)).detach().to(torch.float32))
+                return bank
             bank = self._banks[flat] = self._encode(flat).detach().to(torch.float32)
         return bank
+
+    def _plan_for(self, sample):
+        """The packing plan of the bank ``_bank_for(sample)`` returns (prompt_groups only)."""
+        texts = _meta_of(sample).get("texts") if sample is not None else None
+        return self._plan_cur if texts is None else self._plans[_flat_texts(texts)]
 
     PACKED_BANKS_MAX = 16          # cached combinations (32 banks of 80 rows: 7.9 MB each)
 
@@ -856,6 +889,12 @@ class YOLOWorldDetector(_DeviceModule):
         from . import lib as L
         idxs = list(range(len(xs)))
         packed = self._packed_for(banks, dev)
+        groups_kw = {}
+        if self.prompt_groups:
+            if packed is not None:
+                raise NotImplementedError("prompt_groups=True with differing class lists in one batch is not implemented (one "
+                                          "packing plan per step); batch images of one class list")
+            groups_kw = dict(prompt_groups=self._plan_for(samples[0]))
         chw = torch.stack([xs[i].to(dev) for i in idxs])     # [b, 3, H, W] BGR, contiguous
         if chw.dtype not in (torch.uint8, torch.float32):
             chw = chw.to(torch.float32)
@@ -874,7 +913,7 @@ class YOLOWorldDetector(_DeviceModule):
                                      iou_thr=self.test_cfg["nms"]["iou_threshold"], with_embed=False,
                                      # mmdet _bbox_post_process -> mmcv.ops.batched_nms(bboxes, scores, labels, cfg.nms)
                                      nms="mmcv", nms_param=int(self.test_cfg["nms"].get("split_thr", 10000)), **self._best_kw(),
-                                     **self._sparse_kw(), **(dict(top_names=self.top_names) if self.top_names else {}))
+                                     **self._sparse_kw(), **(dict(top_names=self.top_names) if self.top_names else {}), **groups_kw)
         res = run()
         recal = (lambda: self._h.recalibrate(tower, x)) if self._h.auto_calibrate else None
         counts = tower.checked_counts(res, run, recal)
@@ -905,6 +944,7 @@ class YOLOWorldDetector(_DeviceModule):
         the stream's counters when it ends."""
         self._refuse_top_names("predict_stream")
         self._refuse_sparse("predict_stream")
+        self._refuse_groups("predict_stream")
         from .stream import MmdetBackend, predict_stream
         return predict_stream(MmdetBackend(self, pipeline_cfg, rescale), data_infos, batch_size, decode_workers, stats)
 
@@ -918,8 +958,14 @@ class YOLOWorldDetector(_DeviceModule):
             raise NotImplementedError(f"{what} with top_names={self.top_names} is not implemented (its packed result blobs do not "
                                       "carry the name lists; use predict)")
 
+    def _refuse_groups(self, what: str) -> None:
+        if self.prompt_groups:
+            raise NotImplementedError(f"{what} with prompt_groups=True is not implemented (its steps score one row per class; use "
+                                      "predict)")
+
     def _refuse_best(self, what: str) -> None:
         self._refuse_top_names(what)
+        self._refuse_groups(what)
         if self.best_class:
             raise NotImplementedError(f"{what} with best_class=True is not implemented (the merges rank (anchor, class) candidates)")
         self._refuse_sparse(what)

@@ -280,6 +280,11 @@ class ImageTower:
         self._topn_key: Optional[torch.Tensor] = None         # top-n keys int64 [B * N * 8] and the kept lists, allocated by the first topn_scores()
         self._topn_out_score: Optional[torch.Tensor] = None
         self._topn_out_label: Optional[torch.Tensor] = None
+        self._group_out: Optional[torch.Tensor] = None        # class scores fp32 [B * N * G] of a prompt-groups step, allocated / grown by group_scores()
+        # $WEDETECT_GROUP_FUSED=1: the fused class-max launch (wd_group_similarity_split).  Off by default: the launch costs 1.26 x
+        # wd_similarity_split on the same operands (profiles/prompt_groups.txt), so the fp16x3 path takes
+        # wd_similarity_split blocks into ``self.scores`` + wd_group_rows; same bits either way
+        self.group_fused = os.environ.get("WEDETECT_GROUP_FUSED", "0") == "1"
         # sparse scores (detect(sparse_scores=True), include/wedetect_hip_sparse.h): per-image candidate lists int64 [B, cap],
         # counters int32 [B, 2] and select status int32 [B], allocated by the first sparse_candidates()
         self._sparse_list: Optional[torch.Tensor] = None
@@ -1663,6 +1668,62 @@ class ImageTower:
             return self._result(with_embed, top_scores=ts, top_labels=tl)
         return self._result(with_embed)
 
+    # ------------------------------------------------------------------ prompt groups (a class scored as the best of its names)
+    def _grow_topk_ws(self, k: int) -> None:
+        """``topk_ws`` for B x N x k scores, where it is smaller (``_alloc_post`` sizes it for ``max_classes``)."""
+        nbytes = L.topk_workspace_bytes(self.B, self.ntot * k, self.nms_pre)
+        if nbytes > self.topk_ws.numel():
+            ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.dev)
+            off = (-ws.data_ptr()) % 256
+            self.topk_ws = ws[off:off + nbytes]
+            self.generation += 1
+
+    def group_scores(self, text: torch.Tensor, groups, normalize: bool) -> torch.Tensor:
+        """Class scores [B, N, G] of the last head for a bank of prompt groups (include/wedetect_hip_groups.h): ``text`` [K_pad, 768]
+        is the PADDED bank of ``groups`` (a ``groups.PromptGroups``: ``groups.pad_bank(bank_flat)``), and element (b, n, g) is the
+        maximum over the rows of class g of the score ``similarity()`` would have stored — the same bits as a class-wise ``amax``
+        over that tensor, which is never written.  Stands where ``similarity()`` stands, behind ``wait_post()``; ``postprocess()``
+        takes the result as it takes ``similarity()``'s.
+
+        One bank of at least SIM_SPLIT_MIN rows on an fp16x3 tower with ``group_fused`` ($WEDETECT_GROUP_FUSED=1; off by default,
+        see __init__): ``wd_group_similarity_split``, chunks of 2^20 bank rows.  Everything else (the default, smaller banks,
+        ``precision='fp32'``, the fp32 fallback): the similarity launch of that path — ``wd_similarity_split`` on the fp16x3 path —
+        into ``self.scores`` in blocks of at most 4096 bank rows, then ``wd_group_rows``.  Both chunk sizes are multiples of 32, so
+        no class is cut, and every path gives the same bits.  The result lives in a tower-owned buffer that is NOT ``self.scores`` (the block path's
+        scratch); it grows like the others, and a growth bumps ``generation``."""
+        from . import groups as PG
+        if text.dim() == 3:
+            raise NotImplementedError("prompt_groups with per-image banks is not implemented (one packing plan per step)")
+        k = self._check_shared_bank(text)
+        if not isinstance(groups, PG.PromptGroups) or k != groups.K_pad:
+            raise L.WedetectHipError(f"prompt groups: the bank has {k} rows, the plan {getattr(groups, 'K_pad', None)!r} "
+                                     "(pass groups.pad_bank(bank_flat))")
+        self.wait_post()
+        rows, G = self.B * self.ntot, groups.G
+        if self._group_out is None or self._group_out.numel() < rows * G:
+            self._group_out = torch.empty(rows * G, dtype=torch.float32, device=self.dev)
+            self.generation += 1
+        self._grow_topk_ws(G)
+        out = self._group_out[: rows * G].view(self.B, self.ntot, G)
+        _, go, bf = groups.device(self.dev)
+
+        def fused(t_split, unscale, kc, c0, seg):
+            if self.group_fused:
+                PG.group_similarity_split(self.embed_s, rows, t_split, unscale, kc, EMBED_DIM, go, bf, c0, out, G, G, seg=seg,
+                                          range_flag=self.range_flag, t_row=c0)
+                return
+            blk = self._scores_block(kc)                  # the two-launch form on the same operands
+            L.similarity_split(self.embed_s, rows, t_split[c0 * EMBED_DIM * 4:], unscale, blk, kc, EMBED_DIM, kc, seg=seg,
+                               range_flag=self.range_flag)
+            PG.group_rows(blk, rows, kc, kc, go, bf, c0, out, G, G)
+
+        def block(blk, kc, c0, counts):
+            PG.group_rows(blk, rows, kc, kc, go, bf, c0, out, G, G)
+
+        self._score_bank(text, normalize, None, (fused, block, PG.FUSED_CHUNK if self.group_fused else PG.ROWS_CHUNK, PG.ROWS_CHUNK),
+                         whole=False)
+        return out
+
     # ------------------------------------------------------------------ sparse scores (multi-label without the score tensor)
     def sparse_candidates(self, text: torch.Tensor, normalize: bool, score_thr: float, text_counts: Optional[torch.Tensor] = None,
                           sparse_cap: int = 65536) -> torch.Tensor:
@@ -1836,7 +1897,8 @@ class ImageTower:
     def detect(self, images_u8, text, meta, *, normalize_text: bool, score_thr: float, iou_thr: float = 0.7,
                with_embed: bool = False, nms: Optional[str] = None, nms_param: Optional[int] = None, nms_device: str = "cpu",
                overlap_post: bool = False, text_counts: Optional[torch.Tensor] = None, best_class: bool = False,
-               agnostic_nms: bool = False, sparse_scores: bool = False, sparse_cap: int = 65536, top_names: int = 0):
+               agnostic_nms: bool = False, sparse_scores: bool = False, sparse_cap: int = 65536, top_names: int = 0,
+               prompt_groups=None):
         """The whole step.  ``text`` [K, 768] (one bank) or [B, k_max, 768] with ``text_counts`` (one bank per image, see
         similarity(); in line and under ``overlap_post`` alike, same bits).  ``nms`` None picks the library the reference's path of this text handling uses: normalised
         text = BNContrastiveHead of the mmdet path -> "mmcv"; prompts as stored = the Uni scripts -> "torchvision".
@@ -1868,7 +1930,17 @@ class ImageTower:
 
         ``top_names`` = n in 1..8 (with ``best_class``): the best-class step whose score launch keeps the n best (score, class) pairs of
         every region — ``topn_scores()`` stands where ``best_scores()`` stands.  Every field of the best-class step is unchanged bit
-        for bit; the result gains ``top_scores`` / ``top_labels`` [B, max_out, n], column 0 being ``scores`` / ``labels``.  0: off."""
+        for bit; the result gains ``top_scores`` / ``top_labels`` [B, max_out, n], column 0 being ``scores`` / ``labels``.  0: off.
+
+        ``prompt_groups`` (a ``groups.PromptGroups``; ``text`` is then its padded bank [K_pad, 768]): the multi-label step in which a
+        class is scored as the best of its prompts — ``group_scores()`` stands where ``similarity()`` stands and hands
+        ``postprocess()`` a [B, N, G] tensor, so labels are class indices in [0, G).  Eager, on the unfolded head; exclusive with
+        ``best_class``, ``sparse_scores`` and ``top_names``; one shared bank only."""
+        if prompt_groups is not None:
+            if best_class or sparse_scores or top_names:
+                raise ValueError("prompt_groups is a multi-label dense step of its own: it excludes best_class, sparse_scores and top_names")
+            if text.dim() == 3 or text_counts is not None:
+                raise NotImplementedError("prompt_groups with per-image banks (text [B, k, 768] / text_counts) is not implemented")
         if isinstance(top_names, bool) or not isinstance(top_names, int) or not 0 <= top_names <= 8:
             raise ValueError(f"top_names must be an int in 0..8, got {top_names!r}")
         if top_names and not best_class:
@@ -1886,7 +1958,7 @@ class ImageTower:
         num_classes = None if (text.dim() == 3 or text_counts is not None) else text.shape[0]
         # the bank folded into the embedding conv (None: this step runs the unfolded path); folded here, on the caller's stream,
         # ahead of the backbone every later stream of the step waits for
-        fold = None if (best_class or sparse) else self._fold_for(text, text_counts, normalize_text)
+        fold = None if (best_class or sparse or prompt_groups is not None) else self._fold_for(text, text_counts, normalize_text)
         # the stage of this step: ``score()`` stands behind the head, ``post(what score() returned)`` on the post-process's stream
         if best_class and top_names:
             score = lambda: self.topn_scores(text, normalize_text, top_names, text_counts=text_counts)
@@ -1898,6 +1970,9 @@ class ImageTower:
         elif sparse:
             score = lambda: self.sparse_candidates(text, normalize_text, score_thr, text_counts=text_counts, sparse_cap=sparse_cap)
             post = lambda _: self.postprocess_sparse(text, meta, iou_thr, with_embed, nms, nms_param, nms_device)
+        elif prompt_groups is not None:
+            score = lambda: self.group_scores(text, prompt_groups, normalize_text)
+            post = lambda scores: self.postprocess(scores, score_thr, meta, iou_thr, with_embed, nms, nms_param, nms_device)
         else:
             score = lambda: self.similarity(text, normalize=normalize_text, text_counts=text_counts, _fold=fold)
             post = lambda scores: self.postprocess(scores, score_thr, meta, iou_thr, with_embed, nms, nms_param, nms_device)
