@@ -340,11 +340,11 @@ ACCESS = {
 # word that only ever receives a plain store of the constant 1 (any order, any number of times, the same bytes; nothing in a
 # kernel reads it).  Nothing else may be A.
 BENIGN = [
-    ("lib.conv_gemm", "range_flag", "csrc/split_gemm_impl.h:106, 232, 316, 430 and csrc/split_epi_oct.h:25 — `if (non-finite) *p.range_flag = 1u;`, csrc/split_gemm_p8.hip:143 — `if (bad) *p.range_flag = 1u;`"),
+    ("lib.conv_gemm", "range_flag", "csrc/split_gemm_impl.h:106, 232, 316, 430 and csrc/split_epi_oct.h:25 — `if (non-finite) *p.range_flag = 1u;`, csrc/split_gemm_p8.hip:157 — `if (bad) *p.range_flag = 1u;`"),
     ("lib.mlp_fused", "range_flag", "csrc/split_gemm_mlp.hip:236 — `pe.range_flag = q.range_flag`: the epilogues of split_gemm_impl.h above"),
     ("lib.mlp_fused_wide", "range_flag", "csrc/split_gemm_mlpw.hip:581 — `pe.range_flag = q.range_flag`: the epilogues of split_gemm_impl.h above"),
     ("lib.mlp_fused_wide_ln", "range_flag", "csrc/split_gemm_mlpw.hip:581 — the same launcher"),
-    ("lib.similarity_split", "range_flag", "csrc/split_gemm_p8.hip:704 -> :143 — `if (bad) *p.range_flag = 1u;`"),
+    ("lib.similarity_split", "range_flag", "csrc/split_gemm_impl.h:106 — `if (non-finite) *p.range_flag = 1u;` in epi_quad, the storing epilogue of wd_launch_p8_similarity"),
     ("fold.fold_similarity", "range_flag", "wd_conv_gemm_split's implicit-GEMM kernel: the epilogues of split_gemm_impl.h / split_epi_oct.h above"),
 ]
 

@@ -3,11 +3,8 @@
 //   wd_best_rows               the same merge from a materialised score block: one wave per row
 //   wd_best_unpack             keys -> (score, label)
 // (wd_nms_gather_labeled lives beside the kernel it is a form of: postprocess.hip.)
-#include "common.h"
+#include "p8_score_launch.h"
 #include "wedetect_hip_best.h"
-
-int wd_launch_p8_best(const WdConvGemm& p, const void* t_split, float unscale, unsigned long long* key, int cls_offset,
-                      hipStream_t st);   // split_gemm_p8.hip
 
 namespace {
 
@@ -59,7 +56,7 @@ extern "C" int wd_best_similarity_split(const void* e_split, int64_t rows, const
   if (wd_similarity_problem(p, e_split, rows, t_split, unscale, n_cls, dim, seg_rows, seg_end0, seg_end1, seg_scale, seg_bias, 1, range_flag) != WD_OK)
     return WD_ERR_BAD_ARG;
   if (!key || cls_offset < 0 || (long long)cls_offset + n_cls > 0x7fffffffLL || (reinterpret_cast<uintptr_t>(key) & 7u)) return WD_ERR_BAD_ARG;
-  if ((unsigned long long)((n_cls + 7) & ~7) * (unsigned long long)((dim + 15) / 16 * 16) * 4ull >= (1ull << 32)) return WD_ERR_UNSUPPORTED;
+  if (!wd_similarity_bank_fits(n_cls, dim)) return WD_ERR_UNSUPPORTED;
   return wd_launch_p8_best(p, t_split, unscale, reinterpret_cast<unsigned long long*>(key), cls_offset,
                            static_cast<hipStream_t>(stream));
 }

@@ -53,9 +53,9 @@ static inline int wd_set_max_lds(WdAttrOnce& once, const void* fn, int bytes) {
 
 static inline bool wd_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-// The problem of a rows x classes similarity launch on the pre-split 256 x 256 kernel — wd_similarity_split and its best-class and
-// candidate forms (wd_best_similarity_split, wd_sparse_similarity_split): region rows [rows][dim] as fp16 hi/lo groups, one output
-// column per bank row, the per-level affine of the seg_* group (seg_rows == 0: none).  Checks the arguments the three entries
+// The problem of a rows x classes similarity launch on the pre-split 256 x 256 kernel — wd_similarity_split and its fused forms
+// (wd_best_ / wd_sparse_ / wd_topn_ / wd_group_similarity_split): region rows [rows][dim] as fp16 hi/lo groups, one output
+// column per bank row, the per-level affine of the seg_* group (seg_rows == 0: none).  Checks the arguments the five entries
 // share — WD_ERR_BAD_ARG — and fills ``p``; the output (p.c / p.ldc, or the form's own sink) is the caller's.
 static inline int wd_similarity_problem(WdConvGemm& p, const void* e_split, int64_t rows, const void* t_split, float unscale, int32_t n_cls,
                                         int32_t dim, int32_t seg_rows, int32_t seg_end0, int32_t seg_end1, const float* seg_scale,
@@ -77,6 +77,12 @@ static inline int wd_similarity_problem(WdConvGemm& p, const void* e_split, int6
   }
   p.range_flag = range_flag;
   return WD_OK;
+}
+
+// The kernel addresses the bank of one launch with 32-bit byte offsets: n_cls rows, padded to whole groups of eight, of dim fp16
+// hi/lo pairs padded to whole k16 steps.  The fused entries refuse a larger bank (WD_ERR_UNSUPPORTED); their callers cut it.
+static inline bool wd_similarity_bank_fits(int32_t n_cls, int32_t dim) {
+  return (unsigned long long)((n_cls + 7) & ~7) * (unsigned long long)((dim + 15) / 16 * 16) * 4ull < (1ull << 32);
 }
 
 __device__ __forceinline__ float wd_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }

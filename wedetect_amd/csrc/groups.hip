@@ -1,11 +1,8 @@
 // groups.hip — prompt groups (include/wedetect_hip_groups.h): a class scored as the best of its prompts, [rows][n_groups] scores.
 //   wd_group_similarity_split   the fp16x3 256 x 256 similarity launch with the class-max epilogue (split_gemm_p8.hip: p8_group_epilogue)
 //   wd_group_rows               the same maxima from a materialised block of scores: a (row, class of the bin) pair per lane
-#include "common.h"
+#include "p8_score_launch.h"
 #include "wedetect_hip_groups.h"
-
-int wd_launch_p8_group(const WdConvGemm& p, const void* t_split, float unscale, const int* group_of, const int* bin_first, int cls_offset,
-                       float* out, int ldo, int n_groups, hipStream_t st);   // split_gemm_p8.hip
 
 namespace {
 
@@ -60,7 +57,7 @@ extern "C" int wd_group_similarity_split(const void* e_split, int64_t rows, cons
   if (wd_similarity_problem(p, e_split, rows, t_split, unscale, n_cls, dim, seg_rows, seg_end0, seg_end1, seg_scale, seg_bias, 1, range_flag) != WD_OK)
     return WD_ERR_BAD_ARG;
   if (!group_args_ok(group_of, bin_first, cls_offset, n_cls, out, ldo, n_groups)) return WD_ERR_BAD_ARG;
-  if ((unsigned long long)n_cls * (unsigned long long)((dim + 15) / 16 * 16) * 4ull >= (1ull << 32)) return WD_ERR_UNSUPPORTED;
+  if (!wd_similarity_bank_fits(n_cls, dim)) return WD_ERR_UNSUPPORTED;
   return wd_launch_p8_group(p, t_split, unscale, group_of, bin_first, cls_offset, out, ldo, n_groups, static_cast<hipStream_t>(stream));
 }
 

@@ -5,11 +5,8 @@
 //   wd_sparse_select             per-image sort of the list (bitonic.h: LDS chunks + global strides) and the unpack into the
 //                                buffers wd_nms_gather reads
 #include "bitonic.h"
-#include "common.h"
+#include "p8_score_launch.h"
 #include "wedetect_hip_sparse.h"
-
-int wd_launch_p8_sparse(const WdConvGemm& p, const void* t_split, float unscale, unsigned long long* list, int list_cap, int* state,
-                        int rows_per_img, int n_cls_total, int cls_offset, float thr, hipStream_t st);   // split_gemm_p8.hip
 
 namespace {
 
@@ -148,7 +145,7 @@ extern "C" int wd_sparse_similarity_split(const void* e_split, int64_t rows, con
   if (bad_list(list, list_cap, state) || rows_per_img <= 0 || rows % rows_per_img || n_cls_total <= 0) return WD_ERR_BAD_ARG;
   if (cls_offset < 0 || (long long)cls_offset + n_cls > (long long)n_cls_total) return WD_ERR_BAD_ARG;
   if ((long long)rows_per_img * n_cls_total >= (1LL << 31)) return WD_ERR_UNSUPPORTED;
-  if ((unsigned long long)((n_cls + 7) & ~7) * (unsigned long long)((dim + 15) / 16 * 16) * 4ull >= (1ull << 32)) return WD_ERR_UNSUPPORTED;
+  if (!wd_similarity_bank_fits(n_cls, dim)) return WD_ERR_UNSUPPORTED;
   return wd_launch_p8_sparse(p, t_split, unscale, reinterpret_cast<unsigned long long*>(list), list_cap, state, rows_per_img,
                              n_cls_total, cls_offset, thr, static_cast<hipStream_t>(stream));
 }

@@ -46,8 +46,14 @@
 // position of the same stream, their read / DMA-issue bursts (an LDS-DMA instruction costs 60-185 issue cycles)
 // coincide instead of hiding behind the partner's MFMAs.  The staggered two-barrier form below keeps one wave of
 // every SIMD in its MFMA run while the other issues memory work, which is what the matrix pipe needs.
+//
+// The epilogue is the template parameter EPI: P8Store = the storing epilogues of split_gemm_impl.h (the VAR bits choose among them), or
+// the argument struct of an epilogue that scores the product instead of storing it — retrieval max, best class, candidates, top-n,
+// prompt groups, each defined in front of the kernel; their launch wrappers are at the end of this file (p8_score_launch.h declares them).
 #include <stdlib.h>
+#include "p8_score_launch.h"
 #include "split_gemm_impl.h"
+#include "topn_key.h"
 
 long long wd_p8_workspace_floats();
 
@@ -104,6 +110,14 @@ struct P8Persist {
   int ntiles;            // gang tiles: row panels x column groups
 };
 
+constexpr int P8VAR_DIRECT = 8192;      // with SVAR_CSPLIT: the direct (no LDS transpose) hi/lo epilogue; GELU / no activation only
+
+// ---- the epilogues that do not store the product: one argument struct each (the kernel's template parameter EPI and its argument
+// `ep`) and a function  p8_*_epilogue(p, args, unscale, mw, nw, lane, acc[, patch])  for one wave's 128 x 64 piece of the tile (rows from mw,
+// columns from nw), which the struct's run() hands on to.  PADS_COLUMN_TILES: the launch pads its column tiles to whole groups of eight
+// and the kernel skips them.  A further mode adds its struct and function here and a launcher below; the kernel does not change.
+struct P8Store { static constexpr bool PADS_COLUMN_TILES = false; };
+
 // ---- retrieval scoring on this kernel (round 5; wd_retrieval_max_split, retrieval_metric.py:367-377) ----------------------
 // The GEMM is run with the operand ROLES SWAPPED: the text bank is the "activation" operand (p.a, p.m = classes of this
 // launch) and the region rows of all images, back to back, are the "weight" operand (wsp, p.n = region rows).  In the
@@ -115,21 +129,18 @@ struct P8Persist {
 // Tile order: region-row tiles in groups of eight, four bank blocks x eight row tiles live per XCD at a time (the gang
 // order of the MLP launches): per 32 tiles an L2 fetches 12 operand panels instead of 33, the bank streams from HBM once per
 // row-tile group (five times for 32 images x 300 regions), the region rows (29 MB) stay in the Infinity Cache.
-constexpr int P8VAR_RETR = 4096;
-constexpr int P8VAR_DIRECT = 8192;      // with SVAR_CSPLIT: the direct (no LDS transpose) hi/lo epilogue; GELU / no activation only
-// One argument block for the epilogues that do not store the product; a launch fills its own members.  RETR: scale, bias [region rows]
-// (logit scale applied as exp(scale)); count [images]: valid rows of an image (the first count[i] of its rows_per_img); out [images][ldo]
-// zero-filled: max over an image's valid rows of sigmoid(<e, t> exp(scale) + bias).  BEST / SPARSE / GROUP: see their epilogues below.
-struct P8Retr {
-  union { const float* scale; const int* group_of; }; union { const float* bias; const int* bin_first; };
-  union { const int* count; int* state; };
-  union { float* out; unsigned long long* key; unsigned long long* list; };
-  int rows_per_img; union { int ldo; int cls_offset; };
-  union { int n_cls_total; int ldg; }; union { int list_cap; int n_groups; }; float thr;
+struct P8RetrMax {
+  static constexpr bool PADS_COLUMN_TILES = true;
+  const float* scale;    // [region rows]: logit scale, applied as exp(scale)
+  const float* bias;     // [region rows]
+  const int* count;      // [images]: valid rows of an image (the first count[i] of its rows_per_img)
+  float* out;            // [images][ldo], zero-filled: max over an image's valid rows of sigmoid(<e, t> exp(scale) + bias)
+  int rows_per_img, ldo;
+  template <int TM, int TN> static __device__ __forceinline__ void run(const WdConvGemm& p, const P8RetrMax& a, float unscale, int mw, int nw, int lane,
+      const f32x16 (&acc)[TM][TN], float* patch) { p8_retr_epilogue(p, a, unscale, mw, nw, lane, acc); }
 };
-
 template <int TM, int TN>
-__device__ __forceinline__ void p8_retr_epilogue(const WdConvGemm& p, const P8Retr& rt, float unscale, int mw, int nw, int lane,
+__device__ __forceinline__ void p8_retr_epilogue(const WdConvGemm& p, const P8RetrMax& rt, float unscale, int mw, int nw, int lane,
                                                  const f32x16 (&acc)[TM][TN]) {
   const int nrows = p.n;
   if (nw >= nrows || mw >= p.m) return;                            // wave-uniform
@@ -197,20 +208,365 @@ __device__ __forceinline__ void p8_retr_epilogue(const WdConvGemm& p, const P8Re
   }
 }
 
-constexpr int P8VAR_BEST = 16384;       // best class per region row (wd_best_similarity_split): p8_best_epilogue, at the end of this file
+// ---- what the four epilogues of the similarity launch share ---------------------------------------------------------------------
+// Operands NOT swapped: in the accumulator layout the region row is the LANE (lane & 31) and the class the REGISTER — element
+// e = 16 j + 4 g + q of row tile i is register 4 g + q of acc[i][j] and column p8_col(e) past the lane's first one,
+// c_lane = nw + 4 (lane >> 5) — so a lane holds 32 of the wave's 64 classes for each of its TM rows, and both half-waves hold the
+// same 32 rows of tile i.
+
+// The score of accumulator element v of a row: the expressions of the materialising epilogue (epi_quad<WD_ACT_NONE, true>), so the
+// bits it would have stored.
+__device__ __forceinline__ float p8_score(float v, float unscale, const EpiRow& er) {
+  float x = fmaf(v, unscale, 0.0f);                                // unscale is a power of two: exact
+  x = fmaf(x, er.oscale, er.obias);
+  return wd_sigmoid_fast(x);
+}
+
+__device__ __forceinline__ unsigned long long p8_umax64(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
+__device__ __forceinline__ unsigned p8_col(int e) { return (unsigned)(32 * (e >> 4) + 8 * ((e >> 2) & 3) + (e & 3)); }
+
+// key of element e = score bits << 32 | (0xFFFFFFFF - class), inv0 = 0xFFFFFFFF - cls_offset - c_lane: scores are >= +0, so the
+// unsigned order of the keys is (score ascending, class descending) and a 64-bit max keeps the LOWEST class among equal scores
+__device__ __forceinline__ unsigned long long p8_key(unsigned score_bits, unsigned inv0, int e) {
+  return ((unsigned long long)score_bits << 32) | (unsigned long long)(inv0 - p8_col(e));
+}
+
+// The 32 scores of (lane, row tile i), a = acc[i]: each(e, score, column valid) per element, e ascending; returns whether a valid
+// quad of the row holds a non-finite accumulator (an fp16 half that overflowed).  Fully unrolled: e and every register index are
+// compile-time constants in the caller, nothing is indexed dynamically.  P8Sparse and P8Topn open with it; P8Best writes the same walk
+// out (one register less), P8Group has another shape.
+template <int TN, typename F>
+__device__ __forceinline__ bool p8_score_tile(const WdConvGemm& p, const f32x16 (&a)[TN], float unscale, const EpiRow& er, bool row_ok,
+                                              int c_lane, F&& each) {
+  bool bad = false;
+#pragma unroll
+  for (int j = 0; j < TN; ++j)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int cq = c_lane + 32 * j + 8 * g;
+      if (cq < p.n && row_ok) bad |= wd_any_nonfinite4(a[j][4 * g], a[j][4 * g + 1], a[j][4 * g + 2], a[j][4 * g + 3]);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) each(16 * j + 4 * g + q, p8_score(a[j][4 * g + q], unscale, er), cq + q < p.n);
+    }
+  return bad;
+}
+
+// ---- best class per region row on this kernel (wd_best_similarity_split, include/wedetect_hip_best.h) -----------------------
+// The similarity launch with another epilogue.  Every valid element gets the score the materialising epilogue would have stored
+// (epi_quad<WD_ACT_NONE, true>: fmaf(v, unscale, 0), fmaf(x, oscale, obias), wd_sigmoid_fast — the same expressions, so the same
+// bits), packed as p8_key.  31 in-register maxima, one exchange with the other half-wave, then ONE 64-bit vector atomic max per
+// (row, wave) into key[row] — max is order-independent: the result does not depend on the tile order or on how the bank is cut into
+// launches.  A row with a non-finite accumulator (an fp16 half that overflowed) gets NaN score bits, which beat every score: the
+// unpacked score is then non-finite and wd_topk_candidates reports the image.
+struct P8Best {
+  static constexpr bool PADS_COLUMN_TILES = false;
+  unsigned long long* key;     // [region rows]
+  int cls_offset;              // the class of the launch's first bank row
+  template <int TM, int TN> static __device__ __forceinline__ void run(const WdConvGemm& p, const P8Best& a, float unscale, int mw, int nw, int lane,
+      const f32x16 (&acc)[TM][TN], float* patch) { p8_best_epilogue(p, a, unscale, mw, nw, lane, acc); }
+};
 template <int TM, int TN>
-__device__ __forceinline__ void p8_best_epilogue(const WdConvGemm& p, unsigned long long* __restrict__ key, int cls_offset, float unscale,
-                                                 int mw, int nw, int lane, const f32x16 (&acc)[TM][TN]);
+__device__ __forceinline__ void p8_best_epilogue(const WdConvGemm& p, const P8Best& a, float unscale, int mw, int nw, int lane,
+                                                 const f32x16 (&acc)[TM][TN]) {
+  if (mw >= p.m || nw >= p.n) return;                              // wave-uniform
+  unsigned long long* __restrict__ key = a.key;
+  const int half = lane >> 5;
+  const int c_lane = nw + 4 * half;
+  const unsigned inv0 = 0xFFFFFFFFu - (unsigned)a.cls_offset - (unsigned)c_lane;
+#pragma unroll
+  for (int i = 0; i < TM; ++i) {
+    const int m = mw + 32 * i + (lane & 31);
+    const EpiRow er = epi_row<true>(p, m < p.m ? m : p.m - 1);      // rows past the end: what the padded buffer holds there is not ours to judge
+    unsigned long long best = 0ull;                                // 0 = no class seen
+    bool bad = false;        // p8_score_tile written out (through it this kernel needs 215 registers, so 214): a change there is mirrored HERE
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int cq = c_lane + 32 * j + 8 * g;
+        if (cq < p.n && m < p.m) bad |= wd_any_nonfinite4(acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const unsigned long long kq = p8_key(__float_as_uint(p8_score(acc[i][j][4 * g + q], unscale, er)), inv0, 16 * j + 4 * g + q);
+          best = p8_umax64(best, cq + q < p.n ? kq : 0ull);
+        }
+      }
+    if (bad) {
+      if (p.range_flag) *p.range_flag = 1u;
+      best = (0x7FC00000ull << 32) | (unsigned long long)inv0;
+    }
+    const unsigned olo = __shfl_xor((unsigned)best, 32, 64), ohi = __shfl_xor((unsigned)(best >> 32), 32, 64);
+    best = p8_umax64(best, ((unsigned long long)ohi << 32) | olo);
+    if ((i & 1) == half && m < p.m && best != 0ull) atomicMax(key + m, best);
+  }
+}
 
-constexpr int P8VAR_SPARSE = 32768;     // candidates above a threshold (wd_sparse_similarity_split): p8_sparse_epilogue, at the end of this file
-template <int TM, int TN> __device__ __forceinline__ void p8_sparse_epilogue(const WdConvGemm& p, const P8Retr& rt, float unscale, int mw, int nw, int lane, const f32x16 (&acc)[TM][TN]);
-constexpr int P8VAR_TOPN = 65536; template <int TM, int TN> __device__ __forceinline__ void p8_topn_epilogue(const WdConvGemm& p, const P8Retr& rt, float unscale, int mw, int nw, int lane, const f32x16 (&acc)[TM][TN]); constexpr int P8VAR_GROUP = 131072; template <int TM, int TN> __device__ __forceinline__ void p8_group_epilogue(const WdConvGemm& p, const P8Retr& rt, float unscale, int mw, int nw, int lane, const f32x16 (&acc)[TM][TN], float* patch);   // the n best classes per region row (wd_topn_similarity_split), at the end of this file; P8VAR_GROUP: the best prompt of every class (wd_group_similarity_split), at the end of this file
+// ---- candidates above a threshold on this kernel (wd_sparse_similarity_split, include/wedetect_hip_sparse.h) ----------------
+// Every valid element gets the score the materialising epilogue would have stored (the same three expressions, so the same bits);
+// the 32 scores of (lane, i) replace their accumulators (every index is a compile-time constant: the loops are unrolled, nothing
+// is indexed dynamically) and a 32-bit mask records which of them pass score > thr.
+// Slots: the lanes' popcounts become offsets by an inclusive wave prefix sum (six shuffles); where the wave's 32 rows lie inside ONE
+// image, lane 0 draws the wave's total from state[b][0] with one vector atomic and broadcasts the base — one atomic per
+// (wave, group) however many elements pass.  A group that straddles two images (rows_per_img = 8400 is no multiple of 32) lets
+// every lane with candidates draw its own.  A wave without candidates issues no atomic and skips the stores.  Keys
+// (~score bits << 32 | flat index) go out as plain 8-byte vector stores to list[b][slot] while slot < list_cap; the counter runs
+// on past the cap, which is how wd_sparse_select sees an overflow.
+struct P8Sparse {
+  static constexpr bool PADS_COLUMN_TILES = false;
+  unsigned long long* list;    // [images][list_cap]
+  int* state;                  // [images][2]: candidates seen, non-finite seen
+  int rows_per_img;
+  int cls_offset, n_cls_total; // the class of the launch's first bank row; classes of the whole bank (the pitch of the flat index)
+  int list_cap;
+  float thr;
+  template <int TM, int TN> static __device__ __forceinline__ void run(const WdConvGemm& p, const P8Sparse& a, float unscale, int mw, int nw, int lane,
+      const f32x16 (&acc)[TM][TN], float* patch) { p8_sparse_epilogue(p, a, unscale, mw, nw, lane, acc); }
+};
+template <int TM, int TN>
+__device__ __forceinline__ void p8_sparse_epilogue(const WdConvGemm& p, const P8Sparse& a, float unscale, int mw, int nw, int lane,
+                                                   const f32x16 (&acc)[TM][TN]) {
+  static_assert(TN * 16 == 32, "one 32-bit pass mask per (lane, row tile)");
+  if (mw >= p.m || nw >= p.n) return;                              // wave-uniform
+  unsigned long long* __restrict__ list = a.list;
+  int* __restrict__ state = a.state;
+  const int rpi = a.rows_per_img;
+  const unsigned cap = (unsigned)a.list_cap;
+  const float thr = a.thr;
+  const int half = lane >> 5;
+  const int c_lane = nw + 4 * half;
+#pragma unroll
+  for (int i = 0; i < TM; ++i) {
+    const int m_first = mw + 32 * i;
+    if (m_first >= p.m) break;                                     // wave-uniform
+    const int m_last = m_first + 31 < p.m ? m_first + 31 : p.m - 1;
+    const int b_first = m_first / rpi;
+    const bool one_image = m_last / rpi == b_first;                // wave-uniform
+    const int m = m_first + (lane & 31);
+    const bool row_ok = m < p.m;
+    const int mc = row_ok ? m : p.m - 1;                           // rows past the end: what the padded buffer holds there is not ours to judge
+    const EpiRow er = epi_row<true>(p, mc);
+    const int b = one_image ? b_first : mc / rpi;
+    const unsigned flat0 = (unsigned)(mc - b * rpi) * (unsigned)a.n_cls_total + (unsigned)a.cls_offset + (unsigned)c_lane;
+    float sc[TN * 16];
+    unsigned mask = 0u;
+    const bool bad = p8_score_tile(p, acc[i], unscale, er, row_ok, c_lane, [&](int e, float x, bool col_ok) {
+      sc[e] = x;
+      mask |= (row_ok && col_ok && x > thr) ? (1u << e) : 0u;
+    });
+    if (bad) {
+      if (p.range_flag) *p.range_flag = 1u;
+      state[2 * b + 1] = 1;                                        // sticky, benign race
+    }
+    const unsigned cnt = (unsigned)__popc(mask);
+    if (__ballot(cnt != 0u) == 0ull) continue;                     // wave-uniform: nothing passes in this group
+    unsigned pos;
+    if (one_image) {
+      unsigned incl = cnt;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const unsigned up = __shfl_up(incl, o, 64);
+        incl += lane >= o ? up : 0u;
+      }
+      const unsigned total = __shfl(incl, 63, 64);
+      unsigned base = 0u;
+      if (lane == 0) base = (unsigned)atomicAdd(state + 2 * b_first, (int)total);
+      base = __shfl(base, 0, 64);
+      pos = base + incl - cnt;
+    } else {
+      pos = cnt ? (unsigned)atomicAdd(state + 2 * b, (int)cnt) : 0u;
+    }
+    unsigned long long* __restrict__ lb = list + (size_t)b * cap;
+#pragma unroll
+    for (int e = 0; e < TN * 16; ++e) {
+      if ((mask >> e) & 1u) {
+        if (pos < cap) lb[pos] = ((unsigned long long)(~__float_as_uint(sc[e])) << 32) | (unsigned long long)(flat0 + p8_col(e));
+        ++pos;
+      }
+    }
+  }
+}
 
-template <int VAR, int ABL = 0, bool PERSIST = false>
+// ---- the n best classes per region row on this kernel (wd_topn_similarity_split, include/wedetect_hip_topn.h) ----------------
+// The keys of P8Best.  A lane reads its row's last slot ONCE (device scope) as the bound, marks which of its 32 keys lie above it
+// (after the first column tiles of a row almost none do, and a wave without one leaves here), then selects the marked keys in
+// descending order — one pass over the 32 registers per key, every index a compile-time constant — and offers the t-th of them to
+// the row at slot t (wd_topn_offer, topn_key.h), reading the bound again in between: the other column tiles of the row raise it.
+// A row with a non-finite accumulator gets NaN score bits in slot 0, as in P8Best.
+struct P8Topn {
+  static constexpr bool PADS_COLUMN_TILES = false;
+  unsigned long long* key;     // [region rows][n_top]
+  const float* row_scale;      // [region rows]: the per-row affine, applied as exp(row_scale); both null: the level affine of p
+  const float* row_bias;
+  int cls_offset;              // the class of the launch's first bank row
+  int n_top;
+  template <int TM, int TN> static __device__ __forceinline__ void run(const WdConvGemm& p, const P8Topn& a, float unscale, int mw, int nw, int lane,
+      const f32x16 (&acc)[TM][TN], float* patch) { p8_topn_epilogue(p, a, unscale, mw, nw, lane, acc); }
+};
+template <int TM, int TN>
+__device__ __forceinline__ void p8_topn_epilogue(const WdConvGemm& p, const P8Topn& a, float unscale, int mw, int nw, int lane,
+                                                 const f32x16 (&acc)[TM][TN]) {
+  static_assert(TN * 16 == 32, "one 32-bit mask per (lane, row tile)");
+  if (mw >= p.m || nw >= p.n) return;                              // wave-uniform
+  unsigned long long* key = a.key;
+  const int n_top = a.n_top;
+  const int half = lane >> 5;
+  const int c_lane = nw + 4 * half;
+  const unsigned inv0 = 0xFFFFFFFFu - (unsigned)a.cls_offset - (unsigned)c_lane;
+#pragma unroll
+  for (int i = 0; i < TM; ++i) {
+    if (mw + 32 * i >= p.m) break;                                 // wave-uniform
+    const int m = mw + 32 * i + (lane & 31);
+    const bool row_ok = m < p.m;
+    const int mc = row_ok ? m : p.m - 1;                           // rows past the end: what the padded buffer holds there is not ours to judge
+    EpiRow er = epi_row<true>(p, mc);
+    if (a.row_scale) { er.oscale = expf(a.row_scale[mc]); er.obias = a.row_bias[mc]; }    // wd_topn_affine_score: the same two expressions
+    unsigned long long* slot = key + (size_t)mc * n_top;
+    unsigned long long bound = wd_topn_bound(slot, n_top);
+    unsigned sc[TN * 16];
+    unsigned mask = 0u;
+    const bool bad = p8_score_tile(p, acc[i], unscale, er, row_ok, c_lane, [&](int e, float x, bool col_ok) {
+      sc[e] = __float_as_uint(x);
+      mask |= (row_ok && col_ok && p8_key(sc[e], inv0, e) > bound) ? (1u << e) : 0u;
+    });
+    if (bad) {
+      if (p.range_flag) *p.range_flag = 1u;
+      atomicMax(slot, (0x7FC00000ull << 32) | (unsigned long long)inv0);
+      mask = 0u;
+    }
+    if (__ballot(mask != 0u) == 0ull) continue;                    // wave-uniform: nothing of this group reaches a list
+    unsigned long long prev = ~0ull;
+    for (int t = 0; t < n_top && mask != 0u; ++t) {
+      unsigned long long best = 0ull;
+#pragma unroll
+      for (int e = 0; e < TN * 16; ++e) {
+        const unsigned long long ke = p8_key(sc[e], inv0, e);
+        best = (((mask >> e) & 1u) && ke < prev && ke > best) ? ke : best;
+      }
+      if (t > 0) bound = p8_umax64(bound, wd_topn_bound(slot, n_top));
+      if (best <= bound) break;                                    // descending: no later key of this lane is above the bound either
+      wd_topn_offer(slot, n_top, t, best, bound);
+      prev = best;
+    }
+  }
+}
+
+// ---- the best prompt of every class on this kernel (wd_group_similarity_split, include/wedetect_hip_groups.h) -----------------
+// The layout and the scores of P8Best; the 32 bank rows nw + 32 j .. + 31 of accumulator tile (i, j) are ONE BIN of the packing
+// (cls_offset and nw are multiples of 32), split between lane L and lane L ^ 32.  Which rows of a bin belong to which class depends
+// on the column only: wave-uniform.
+// Per bin (j): the wave reads the bin's classes [g0, g0 + ng) and its 32 group_of words (uniform loads).  The (row, class) pairs
+// of a 32-row tile are dealt in passes of rp = min(32, 64 / ng) rows x ng classes: lane = (row r0 of the pass, class k = lane % ng),
+// the SAME class in every pass, so a lane counts the columns in front of class g0 + k and those of it, (start, ln), once per bin;
+// the longest class of the bin bounds the read loop.
+// Per (i, j): every lane writes its 16 SCORES (p8_score per element: the materialised bits) to the wave's 32 x 36-float patch —
+// the patch of the materialising epilogue, transposed the same way — then, per pass, a lane reads the columns of its class in its
+// row from the patch, four independent reads at a time (a shorter class re-reads its last column: max is idempotent), and stores
+// the maximum at out[row][g0 + k].  Consecutive lanes store consecutive classes of a row: row segments of ng floats, every element
+// written exactly once, no atomics, nothing cleared.  (A first form dealt the pairs 64 per pass with the class changing per
+// pass — a lane exchange and a serial read loop in every pass: 3.53 ms, this form 3.02 ms, against 2.39 ms of the materialising launch on the LVIS
+// plan, profiles/prompt_groups.txt.)  A non-finite accumulator of (row, bin) raises the range flag and turns the row's 32 patch
+// entries into NaN, so every class of the bin gets NaN in that row (fmaxf(NaN, NaN) = NaN).
+// No register is indexed dynamically: i, j, g, q are unrolled, the pass loop touches the patch only.
+struct P8Group {
+  static constexpr bool PADS_COLUMN_TILES = false;
+  const int* group_of;         // [bank rows of the whole bank]: the class of a bank row, non-decreasing
+  const int* bin_first;        // [bins + 1]: the first class of a bin
+  float* out;                  // [region rows][ldg]
+  int cls_offset;              // the bank row of the launch's first one, a multiple of 32
+  int ldg, n_groups;
+  template <int TM, int TN> static __device__ __forceinline__ void run(const WdConvGemm& p, const P8Group& a, float unscale, int mw, int nw, int lane,
+      const f32x16 (&acc)[TM][TN], float* patch) { p8_group_epilogue(p, a, unscale, mw, nw, lane, acc, patch); }
+};
+template <int TM, int TN>
+__device__ __forceinline__ void p8_group_epilogue(const WdConvGemm& p, const P8Group& a, float unscale, int mw, int nw, int lane,
+                                                  const f32x16 (&acc)[TM][TN], float* patch) {
+  if (mw >= p.m || nw >= p.n) return;                              // wave-uniform
+  const int half = lane >> 5, l31 = lane & 31;
+  const float qnan = __uint_as_float(0x7FC00000u);
+#pragma unroll
+  for (int j = 0; j < TN; ++j) {
+    const int c0 = nw + 32 * j;                                    // first bank row of the bin, in this launch
+    if (c0 >= p.n) break;                                          // wave-uniform (p.n is a multiple of 32: a bin is in or out)
+    const int abin = (a.cls_offset + c0) >> 5;
+    const int g0 = a.bin_first[abin];
+    int ng = a.bin_first[abin + 1] - g0;
+    ng = (g0 < 0 || ng < 0) ? 0 : (ng > 32 ? 32 : ng);             // a table that is no plan's: nothing is stored
+    ng = __builtin_amdgcn_readfirstlane(ng);
+    if (ng == 0) continue;
+    // the (row, class) pairs of a pass: rp = min(32, 64 / ng) rows of ng classes; lane = (row r0 of the pass, class k), the same
+    // class in every pass, so its column range is found once per bin
+    const int magic = (65536 + ng - 1) / ng;                       // x / ng = (x * magic) >> 16 for x < 1024, ng <= 32
+    const int rp = ng <= 2 ? 32 : (64 * magic) >> 16;
+    const int r0 = (lane * magic) >> 16;
+    const int k = lane - r0 * ng;
+    const int* __restrict__ go = a.group_of + a.cls_offset + c0;
+    const int mine = g0 + k;
+    int start = 0, end = 0, run = 0, maxl = 1, prev = 0;
+#pragma unroll
+    for (int c = 0; c < 32; ++c) {
+      const int gc = go[c];
+      start += gc < mine ? 1 : 0;
+      end += gc <= mine ? 1 : 0;
+      run = (c > 0 && gc == prev) ? run + 1 : 1;
+      maxl = run > maxl ? run : maxl;
+      prev = gc;
+    }
+    maxl = __builtin_amdgcn_readfirstlane(maxl);
+    const int ln = end - start, last = ln > 0 ? ln - 1 : 0;        // columns of class g0 + k: [start, start + ln); ln = 0: a table that is no plan's
+    const bool lane_ok = r0 < rp && ln > 0 && g0 + k < a.n_groups;
+    const int o1 = last < 1 ? last : 1, o2 = last < 2 ? last : 2, o3 = last < 3 ? last : 3;
+    const int lane_off = (r0 < 32 ? r0 : 0) * EPI_LDT + start;     // start + last <= 31; ln = 0: start <= 32, inside the 36-float pitch
+    float* const outk = a.out + g0 + k;
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+      const int m_first = mw + 32 * i;
+      if (m_first >= p.m) break;                                   // wave-uniform
+      const int m = m_first + l31;
+      const bool row_ok = m < p.m;
+      const EpiRow er = epi_row<true>(p, row_ok ? m : p.m - 1);     // rows past the end: what the padded buffer holds there is not ours to judge
+      bool bad = false;
+#pragma unroll
+      for (int g = 0; g < 4; ++g)
+        bad |= wd_any_nonfinite4(acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]);
+      bad = bad && row_ok;
+      bad = bad || (__shfl_xor((int)bad, 32, 64) != 0);            // the other 16 bank rows of the bin
+      if (bad && p.range_flag) *p.range_flag = 1u;
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        f32x4 s;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) s[q] = bad ? qnan : p8_score(acc[i][j][4 * g + q], unscale, er);
+        *reinterpret_cast<f32x4*>(patch + l31 * EPI_LDT + 8 * g + 4 * half) = s;
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      for (int rb = 0; rb < 32; rb += rp) {
+        const int r = rb + r0;                                     // row of the tile
+        const float* src = patch + (r < 32 ? rb : 0) * EPI_LDT + lane_off;
+        // four independent reads (a class of fewer columns re-reads its last one: max is idempotent), then the rare long classes
+        const float v0 = src[0], v1 = src[o1], v2 = src[o2], v3 = src[o3];
+        float v = fmaxf(fmaxf(v0, v1), fmaxf(v2, v3));
+        for (int t = 4; t < maxl; t += 4) {
+          const float w0 = src[t < last ? t : last], w1 = src[t + 1 < last ? t + 1 : last], w2 = src[t + 2 < last ? t + 2 : last],
+                      w3 = src[t + 3 < last ? t + 3 : last];
+          v = fmaxf(v, fmaxf(fmaxf(w0, w1), fmaxf(w2, w3)));
+        }
+        const int mm = m_first + r;
+        if (lane_ok && r < 32 && mm < p.m) outk[(size_t)mm * a.ldg] = v;
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+  }
+}
+
+template <int VAR, typename EPI = P8Store, int ABL = 0, bool PERSIST = false>
 __global__ void __launch_bounds__(512, 2)
 split_gemm_p8_kernel(const WdConvGemm p, const unsigned char* __restrict__ wsp, int k16, float unscale, int nbn,
-                     int vec_c, int vec_res, int vec_bias, int ngrp, int nbm, const P8Persist ps, const P8Retr rt, int stagger,
-                     int arows, int wrows) {
+                     int vec_c, int vec_res, int vec_bias, int ngrp, int nbm, const P8Persist ps, int stagger,
+                     int arows, int wrows, const EPI ep) {
   constexpr int TM = 4, TN = 2, BM = 256, BN = 256, ROWB = P8_ROWB;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int t = threadIdx.x, lane = t & 63;
@@ -286,7 +642,7 @@ split_gemm_p8_kernel(const WdConvGemm p, const unsigned char* __restrict__ wsp, 
     const int grp = tile / gsz, rem = tile - grp * gsz;
     const int bm = rem / ngrp, bn = grp * ngrp + (rem - bm * ngrp);
     const int m0 = bm * BM, n0 = bn * BN;
-    if ((VAR & P8VAR_RETR) && n0 >= p.n) continue;               // row-tile groups are padded to eight tiles: nothing to do
+    if (EPI::PADS_COLUMN_TILES && n0 >= p.n) continue;           // column tiles padded to whole groups of eight: nothing to do
 
     // request K tile kt (relative to kb) of one operand region into LDS offset `reg` (buffer / ring slot included):
     // two 1 KB DMAs per wave.  half: 0 = A0 / W0, 1 = A1 / W1.  The 8-row group's first row is wave-uniform and rides
@@ -295,10 +651,9 @@ split_gemm_p8_kernel(const WdConvGemm p, const unsigned char* __restrict__ wsp, 
       if (ABL & 1) return;
       const unsigned char* base = is_w ? wsp : abase;
       const unsigned pitch = (unsigned)(is_w ? k16 : p.lda) * 4u;
-      // retrieval: any row counts — the operand buffers of wd_split_weights are padded to whole groups of eight rows
       // arows / wrows: rows the operand BUFFERS hold, whole groups of eight (= p.m / p.n for the plain launches, which require
-      // multiples of eight; the similarity launch and the retrieval pad their buffers instead)
-      const int limit = (VAR & P8VAR_RETR) ? (((is_w ? p.n : p.m) + 7) & ~7) - 8 : (is_w ? wrows : arows) - 8;
+      // multiples of eight; the similarity launches and the retrieval pad their buffers instead)
+      const int limit = (is_w ? wrows : arows) - 8;
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         int row = is_w ? n0 + (2 * j + (wave >> 2)) * 64 + (wave & 3) * 8 + half * 32 : m0 + j * 128 + wave * 8 + half * 64;
@@ -521,13 +876,10 @@ split_gemm_p8_kernel(const WdConvGemm p, const unsigned char* __restrict__ wsp, 
       if (sum == 12345.678f) p.c[t] = sum;
       continue;
     }
-    if constexpr ((VAR & P8VAR_RETR) != 0) {
-      p8_retr_epilogue<TM, TN>(p, rt, unscale, m0 + group * 128, n0 + wn * 64, lane, acc);
+    if constexpr (!std::is_same_v<EPI, P8Store>) {                  // the product is scored, not stored
+      EPI::run(p, ep, unscale, m0 + group * 128, n0 + wn * 64, lane, acc, reinterpret_cast<float*>(smem_raw) + wave * 32 * EPI_LDT);
       continue;
     }
-    if constexpr ((VAR & P8VAR_BEST) != 0) { p8_best_epilogue<TM, TN>(p, rt.key, rt.cls_offset, unscale, m0 + group * 128, n0 + wn * 64, lane, acc); continue; }
-    if constexpr ((VAR & P8VAR_SPARSE) != 0) { p8_sparse_epilogue<TM, TN>(p, rt, unscale, m0 + group * 128, n0 + wn * 64, lane, acc); continue; }
-    if constexpr ((VAR & P8VAR_TOPN) != 0) { p8_topn_epilogue<TM, TN>(p, rt, unscale, m0 + group * 128, n0 + wn * 64, lane, acc); continue; } if constexpr ((VAR & P8VAR_GROUP) != 0) { p8_group_epilogue<TM, TN>(p, rt, unscale, m0 + group * 128, n0 + wn * 64, lane, acc, reinterpret_cast<float*>(smem_raw) + wave * 32 * EPI_LDT); continue; }
     const EpiVec ev{vec_c, vec_res, vec_bias, unscale};
     const int mw = m0 + group * 128, nw = n0 + wn * 64;
     float* patch = reinterpret_cast<float*>(smem_raw) + wave * 32 * EPI_LDT;
@@ -589,10 +941,12 @@ int p8_stagger() {
 // workgroups of an XCD)
 int p8_gang(int nbn) { return nbn % 8 == 0 ? 8 : nbn % 4 == 0 ? 4 : nbn % 2 == 0 ? 2 : 1; }
 
-template <int VAR, int ABL = 0, bool PERSIST = false>
+// arows / wrows: rows the operand buffers hold where that is not p.m / p.n; ep: the arguments of a scoring epilogue (EPI is deduced)
+template <int VAR, int ABL = 0, bool PERSIST = false, typename EPI = P8Store>
 int launch_p8(const WdConvGemm& p, const void* wsp, float unscale, hipStream_t st, float* ws = nullptr, long long ws_floats = 0,
-              int arows = 0, int wrows = 0, const P8Retr& rt = P8Retr{}) {
-  const int nbm = (p.m + 255) / 256, nbn = (p.n + 255) / 256;
+              int arows = 0, int wrows = 0, const EPI& ep = EPI{}) {
+  const int nbm = (p.m + 255) / 256;
+  const int nbn = EPI::PADS_COLUMN_TILES ? ((p.n + 255) / 256 + 7) / 8 * 8 : (p.n + 255) / 256;
   const long long nblk = (long long)nbm * nbn;
   if (nblk <= 0 || nblk > 0x7fffffffLL) return WD_ERR_BAD_ARG;
   const int k16 = (p.k + 15) / 16 * 16;
@@ -623,28 +977,20 @@ int launch_p8(const WdConvGemm& p, const void* wsp, float unscale, hipStream_t s
     ps.acc = ws + 1024;
     grid = wgs;
   }
-  auto k = split_gemm_p8_kernel<VAR, ABL, PERSIST>;
+  auto k = split_gemm_p8_kernel<VAR, EPI, ABL, PERSIST>;
   static WdAttrOnce attr;
   if (wd_set_max_lds(attr, reinterpret_cast<const void*>(k), P8_LDS) != WD_OK) return WD_ERR_LAUNCH;
   WD_LAUNCH_GEMM(k, dim3((unsigned)grid), dim3(512), P8_LDS, st, p, static_cast<const unsigned char*>(wsp), k16, unscale, nbn,
-                 vec_c, vec_res, vec_bias, ngrp, nbm, ps, rt, p8_stagger(), arows > 0 ? arows : p.m, wrows > 0 ? wrows : p.n);
+                 vec_c, vec_res, vec_bias, ngrp, nbm, ps, p8_stagger(), arows > 0 ? arows : p.m, wrows > 0 ? wrows : p.n, ep);
   return wd_launch_status();
 }
 
-// retrieval scoring: p.a = bank rows [p.m][p.lda] (fp16 hi/lo groups), wsp = region rows [p.n][k16], see P8Retr
-int launch_p8_retr(const WdConvGemm& p, const void* wsp, float unscale, const P8Retr& rt, hipStream_t st) {
-  const int nbm = (p.m + 255) / 256, nbn = ((p.n + 255) / 256 + 7) / 8 * 8;      // row tiles padded to whole groups of eight
-  const long long nblk = (long long)nbm * nbn;
-  if (nblk <= 0 || nblk > 0x7fffffffLL) return WD_ERR_BAD_ARG;
-  const int k16 = (p.k + 15) / 16 * 16;
-  if ((unsigned long long)((p.m + 7) & ~7) * p.lda * 4 >= (1ull << 32) || (unsigned long long)((p.n + 7) & ~7) * k16 * 4 >= (1ull << 32))
-    return WD_ERR_UNSUPPORTED;
-  auto k = split_gemm_p8_kernel<P8VAR_RETR, 0, false>;
-  static WdAttrOnce attr;
-  if (wd_set_max_lds(attr, reinterpret_cast<const void*>(k), P8_LDS) != WD_OK) return WD_ERR_LAUNCH;
-  WD_LAUNCH_GEMM(k, dim3((unsigned)nblk), dim3(512), P8_LDS, st, p, static_cast<const unsigned char*>(wsp), k16, unscale, nbn,
-                 0, 0, 0, 8, nbm, P8Persist{nullptr, nullptr, nullptr, (int)nblk}, rt, 0, 0, 0);
-  return wd_launch_status();
+// the launches that pad their operand buffers to whole groups of eight rows instead of requiring p.m % 8 == p.n % 8 == 0: the
+// similarity launch (EPI = P8Store) and every scoring epilogue.  Retrieval had a launcher of its own that passed stagger = 0 and
+// vec_c = 0: here it gets p8_stagger() (0 but in WD_DEBUG_ABLATIONS builds, where $WD_P8_STAGGER now delays it too) and a vec_c it never reads.
+template <typename EPI>
+int launch_p8_padded(const WdConvGemm& p, const void* wsp, float unscale, hipStream_t st, const EPI& ep) {
+  return launch_p8<0>(p, wsp, unscale, st, nullptr, 0, (p.m + 7) & ~7, (p.n + 7) & ~7, ep);
 }
 
 }  // namespace
@@ -701,7 +1047,7 @@ int wd_launch_p8(const WdConvGemm& p, const void* w, float unscale, bool csplit,
   return persist ? launch_p8<0, 0, true>(p, w, unscale, st, ws, ws_floats) : launch_p8<0>(p, w, unscale, st);
 }
 
-// wd_retrieval_max_split on the 256 x 256 kernel (operand roles swapped, see P8Retr): bank rows [n_cls][dim] as the
+// wd_retrieval_max_split on the 256 x 256 kernel (operand roles swapped, see P8RetrMax): bank rows [n_cls][dim] as the
 // activation operand, region rows [n_rows][dim] as the weight operand; out [images][ldo] must be zero.  Needs dim % 32 == 0,
 // 16-byte aligned scale / bias, both split buffers padded to whole groups of eight rows (wd_split_weights does that).
 int wd_launch_p8_retrieval(const void* t_split, int n_cls, const void* e_split, int n_rows, int dim, float unscale,
@@ -717,404 +1063,43 @@ int wd_launch_p8_retrieval(const void* t_split, int n_cls, const void* e_split, 
   p.m = n_cls; p.n = n_rows; p.k = dim; p.ldc = ldo;
   p.out_scale = 1.0f;
   p.range_flag = range_flag;
-  return launch_p8_retr(p, e_split, unscale, P8Retr{{scale}, {bias}, {count}, {out}, rows_per_img, {ldo}}, st);
+  return launch_p8_padded(p, e_split, unscale, st, P8RetrMax{scale, bias, count, out, rows_per_img, ldo});
 }
 
 // wd_similarity_split on the 256 x 256 kernel (round 6; yolo_world_head.py:90-108, generate_proposal.py:1129-1131): region rows
 // [rows][dim] as fp16 hi/lo groups (buffer padded to a multiple of eight rows) x text rows [n_cls][dim] split by
 // wd_split_weights_padded; out[row][cls] = (sigmoid)(<e, t> * unscale * seg_scale[level(row)] + seg_bias[level(row)]), the
 // epilogue of the fp32 similarity GEMM.  Ragged n_cls (1203) and ldo are fine (scalar stores when ldo % 4).
-// the three similarity launches: K in whole 32-column steps, row groups of eight, aligned bases, no epilogue but affine + sigmoid
-static bool p8_similarity_ok(const WdConvGemm& p, const void* t_split) {
-  if (p.k % 32 || p.k < 32 || p.lda % 8 || !wd_aligned16(p.a) || !wd_aligned16(t_split)) return false;
-  return !(p.res || p.c2 || p.bias || p.act != WD_ACT_NONE || p.out_mode != WD_OUT_ROWS || p.c_batch_stride > 0 || p.ln_stats);
-}
-
 int wd_launch_p8_similarity(const WdConvGemm& p, const void* t_split, float unscale, hipStream_t st) {
   if (!p8_similarity_ok(p, t_split)) return WD_ERR_UNSUPPORTED;
-  return launch_p8<0>(p, t_split, unscale, st, nullptr, 0, (p.m + 7) & ~7, (p.n + 7) & ~7);
+  return launch_p8_padded(p, t_split, unscale, st, P8Store{});
 }
 
-namespace {
-
-// The members of P8Retr the two epilogues below read: BEST key [region rows], cls_offset (the class of the launch's first bank row);
-// SPARSE list [images][list_cap], state [images][2], rows_per_img, cls_offset, n_cls_total, thr (csrc/sparse.hip).
-// the argument block of split_gemm_p8_kernel, pinned byte for byte: the members of a union share one slot
-static_assert(sizeof(P8Retr) == 56 && offsetof(P8Retr, scale) == 0 && offsetof(P8Retr, bias) == 8 && offsetof(P8Retr, count) == 16 &&
-              offsetof(P8Retr, state) == 16 && offsetof(P8Retr, out) == 24 && offsetof(P8Retr, key) == 24 && offsetof(P8Retr, list) == 24 &&
-              offsetof(P8Retr, rows_per_img) == 32 && offsetof(P8Retr, ldo) == 36 && offsetof(P8Retr, cls_offset) == 36 &&
-              offsetof(P8Retr, n_cls_total) == 40 && offsetof(P8Retr, list_cap) == 44 && offsetof(P8Retr, thr) == 48 &&
-              offsetof(P8Retr, group_of) == 0 && offsetof(P8Retr, bin_first) == 8 && offsetof(P8Retr, ldg) == 40 &&
-              offsetof(P8Retr, n_groups) == 44, "P8Retr layout");
-
-// The score of accumulator element v of a row, for the two epilogues below: the expressions of the materialising epilogue
-// (epi_quad<WD_ACT_NONE, true>), so the bits it would have stored.
-__device__ __forceinline__ float p8_score(float v, float unscale, const EpiRow& er) {
-  float x = fmaf(v, unscale, 0.0f);                                // unscale is a power of two: exact
-  x = fmaf(x, er.oscale, er.obias);
-  return wd_sigmoid_fast(x);
-}
-
-// ---- best class per region row on this kernel (wd_best_similarity_split, include/wedetect_hip_best.h) -----------------------
-// The similarity launch with another epilogue; operands NOT swapped: in the accumulator layout the region row is the LANE
-// (lane & 31) and the class the REGISTER (32 j + 8 g + 4 (lane >> 5) + q in register 4 g + q of acc[i][j]), so a lane holds 32 of
-// the wave's 64 classes for each of its TM rows.  Every valid element gets the score the materialising epilogue would have stored
-// (epi_quad<WD_ACT_NONE, true>: fmaf(v, unscale, 0), fmaf(x, oscale, obias), wd_sigmoid_fast — the same expressions, so the same
-// bits), packed as  key = score bits << 32 | (0xFFFFFFFF - (cls_offset + class)):  scores are >= +0, so the unsigned order of the
-// keys is (score ascending, class descending) and a 64-bit max keeps the LOWEST class among equal scores.  31 in-register maxima, one
-// exchange with the other half-wave, then ONE 64-bit vector atomic max per (row, wave) into key[row] — max is order-independent:
-// the result does not depend on the tile order or on how the bank is cut into launches.  A row with a non-finite accumulator
-// (an fp16 half that overflowed) gets NaN score bits, which beat every score: the unpacked score is then non-finite and
-// wd_topk_candidates reports the image.  (Defined behind its use: the template is declared in front of the kernel.)
-__device__ __forceinline__ unsigned long long p8_umax64(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
-
-template <int TM, int TN>
-__device__ __forceinline__ void p8_best_epilogue(const WdConvGemm& p, unsigned long long* __restrict__ key, int cls_offset, float unscale,
-                                                 int mw, int nw, int lane, const f32x16 (&acc)[TM][TN]) {
-  if (mw >= p.m || nw >= p.n) return;                              // wave-uniform
-  const int half = lane >> 5;
-  const int c_lane = nw + 4 * half;                                // class of (j, g, q) = c_lane + 32 j + 8 g + q
-  const unsigned inv0 = 0xFFFFFFFFu - (unsigned)cls_offset - (unsigned)c_lane;
-#pragma unroll
-  for (int i = 0; i < TM; ++i) {
-    const int m = mw + 32 * i + (lane & 31);
-    const EpiRow er = epi_row<true>(p, m < p.m ? m : p.m - 1);      // rows past the end: what the padded buffer holds there is not ours to judge
-    unsigned long long best = 0ull;                                // 0 = no class seen
-    bool bad = false;
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int cq = c_lane + 32 * j + 8 * g;
-        if (cq < p.n && m < p.m) bad |= wd_any_nonfinite4(acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const float x = p8_score(acc[i][j][4 * g + q], unscale, er);
-          const unsigned long long kq = ((unsigned long long)__float_as_uint(x) << 32) | (unsigned long long)(inv0 - (unsigned)(32 * j + 8 * g + q));
-          best = p8_umax64(best, cq + q < p.n ? kq : 0ull);
-        }
-      }
-    if (bad) {
-      if (p.range_flag) *p.range_flag = 1u;
-      best = (0x7FC00000ull << 32) | (unsigned long long)inv0;
-    }
-    const unsigned olo = __shfl_xor((unsigned)best, 32, 64), ohi = __shfl_xor((unsigned)(best >> 32), 32, 64);
-    best = p8_umax64(best, ((unsigned long long)ohi << 32) | olo);
-    if ((i & 1) == half && m < p.m && best != 0ull) atomicMax(key + m, best);
-  }
-}
-
-}  // namespace
-
-// wd_best_similarity_split: the launch above with the best-class epilogue (p8_best_epilogue) in place of the stores; p.c is unused.
-// The caller has checked n_cls * k16 * 4 < 2^32 (launch_p8 refuses it too: 32-bit DMA offsets from the operand base).
+// The fused forms: the launch above with a scoring epilogue in place of the stores; p.c is unused.  The callers
+// (best.hip, sparse.hip, topn.hip, groups.hip) have checked the sizes, wd_similarity_bank_fits among them (launch_p8 refuses a
+// larger bank too: 32-bit DMA offsets from the operand base).
 int wd_launch_p8_best(const WdConvGemm& p, const void* t_split, float unscale, unsigned long long* key, int cls_offset, hipStream_t st) {
   if (!p8_similarity_ok(p, t_split) || !p.sigmoid || !key || (reinterpret_cast<uintptr_t>(key) & 7u)) return WD_ERR_UNSUPPORTED;
-  P8Retr rt{};
-  rt.key = key; rt.cls_offset = cls_offset;
-  return launch_p8<P8VAR_BEST>(p, t_split, unscale, st, nullptr, 0, (p.m + 7) & ~7, (p.n + 7) & ~7, rt);
+  return launch_p8_padded(p, t_split, unscale, st, P8Best{key, cls_offset});
 }
 
-namespace {
-
-// ---- candidates above a threshold on this kernel (wd_sparse_similarity_split, include/wedetect_hip_sparse.h) ----------------
-// The layout of p8_best_epilogue: the region row is the LANE (lane & 31), the class the REGISTER, both half-waves hold the same 32
-// rows of tile i and 32 classes each.  Every valid element gets the score the materialising epilogue would have stored (the same
-// three expressions, so the same bits); the 32 scores of (lane, i) replace their accumulators (every index is a compile-time
-// constant: the loops are unrolled, nothing is indexed dynamically) and a 32-bit mask records which of them pass score > thr.
-// Slots: the lanes' popcounts become offsets by an inclusive wave prefix sum (six shuffles); where the wave's 32 rows lie inside ONE
-// image, lane 0 draws the wave's total from state[b][0] with one vector atomic and broadcasts the base — one atomic per
-// (wave, group) however many elements pass.  A group that straddles two images (rows_per_img = 8400 is no multiple of 32) lets
-// every lane with candidates draw its own.  A wave without candidates issues no atomic and skips the stores.  Keys
-// (~score bits << 32 | flat index) go out as plain 8-byte vector stores to list[b][slot] while slot < list_cap; the counter runs
-// on past the cap, which is how wd_sparse_select sees an overflow.
-template <int TM, int TN>
-__device__ __forceinline__ void p8_sparse_epilogue(const WdConvGemm& p, const P8Retr& rt, float unscale, int mw, int nw, int lane,
-                                                   const f32x16 (&acc)[TM][TN]) {
-  static_assert(TN * 16 == 32, "one 32-bit pass mask per (lane, row tile)");
-  if (mw >= p.m || nw >= p.n) return;                              // wave-uniform
-  unsigned long long* __restrict__ list = rt.list;
-  int* __restrict__ state = rt.state;
-  const int rpi = rt.rows_per_img;
-  const unsigned cap = (unsigned)rt.list_cap;
-  const float thr = rt.thr;
-  const int half = lane >> 5;
-  const int c_lane = nw + 4 * half;                                // class of (j, g, q) = c_lane + 32 j + 8 g + q
-#pragma unroll
-  for (int i = 0; i < TM; ++i) {
-    const int m_first = mw + 32 * i;
-    if (m_first >= p.m) break;                                     // wave-uniform
-    const int m_last = m_first + 31 < p.m ? m_first + 31 : p.m - 1;
-    const int b_first = m_first / rpi;
-    const bool one_image = m_last / rpi == b_first;                // wave-uniform
-    const int m = m_first + (lane & 31);
-    const bool row_ok = m < p.m;
-    const int mc = row_ok ? m : p.m - 1;                           // rows past the end: what the padded buffer holds there is not ours to judge
-    const EpiRow er = epi_row<true>(p, mc);
-    const int b = one_image ? b_first : mc / rpi;
-    const unsigned flat0 = (unsigned)(mc - b * rpi) * (unsigned)rt.n_cls_total + (unsigned)rt.cls_offset + (unsigned)c_lane;
-    float sc[TN * 16];
-    unsigned mask = 0u;
-    bool bad = false;
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int cq = c_lane + 32 * j + 8 * g;
-        if (cq < p.n && row_ok) bad |= wd_any_nonfinite4(acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const float x = p8_score(acc[i][j][4 * g + q], unscale, er);
-          sc[16 * j + 4 * g + q] = x;
-          mask |= (row_ok && cq + q < p.n && x > thr) ? (1u << (16 * j + 4 * g + q)) : 0u;
-        }
-      }
-    if (bad) {
-      if (p.range_flag) *p.range_flag = 1u;
-      state[2 * b + 1] = 1;                                        // sticky, benign race
-    }
-    const unsigned cnt = (unsigned)__popc(mask);
-    if (__ballot(cnt != 0u) == 0ull) continue;                     // wave-uniform: nothing passes in this group
-    unsigned pos;
-    if (one_image) {
-      unsigned incl = cnt;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const unsigned up = __shfl_up(incl, o, 64);
-        incl += lane >= o ? up : 0u;
-      }
-      const unsigned total = __shfl(incl, 63, 64);
-      unsigned base = 0u;
-      if (lane == 0) base = (unsigned)atomicAdd(state + 2 * b_first, (int)total);
-      base = __shfl(base, 0, 64);
-      pos = base + incl - cnt;
-    } else {
-      pos = cnt ? (unsigned)atomicAdd(state + 2 * b, (int)cnt) : 0u;
-    }
-    unsigned long long* __restrict__ lb = list + (size_t)b * cap;
-#pragma unroll
-    for (int e = 0; e < TN * 16; ++e) {
-      if ((mask >> e) & 1u) {
-        const unsigned flat = flat0 + (unsigned)(32 * (e >> 4) + 8 * ((e >> 2) & 3) + (e & 3));
-        if (pos < cap) lb[pos] = ((unsigned long long)(~__float_as_uint(sc[e])) << 32) | (unsigned long long)flat;
-        ++pos;
-      }
-    }
-  }
-}
-
-}  // namespace
-
-// wd_sparse_similarity_split: the similarity launch with the candidate epilogue (p8_sparse_epilogue) in place of the stores; p.c is
-// unused.  The caller has checked the sizes (csrc/sparse.hip).
 int wd_launch_p8_sparse(const WdConvGemm& p, const void* t_split, float unscale, unsigned long long* list, int list_cap, int* state,
                         int rows_per_img, int n_cls_total, int cls_offset, float thr, hipStream_t st) {
   if (!p8_similarity_ok(p, t_split) || !p.sigmoid || !list || !state) return WD_ERR_UNSUPPORTED;
-  P8Retr rt{};
-  rt.list = list; rt.list_cap = list_cap; rt.state = state;
-  rt.rows_per_img = rows_per_img; rt.n_cls_total = n_cls_total; rt.cls_offset = cls_offset; rt.thr = thr;
-  return launch_p8<P8VAR_SPARSE>(p, t_split, unscale, st, nullptr, 0, (p.m + 7) & ~7, (p.n + 7) & ~7, rt);
+  return launch_p8_padded(p, t_split, unscale, st, P8Sparse{list, state, rows_per_img, cls_offset, n_cls_total, list_cap, thr});
 }
 
-#include "topn_key.h"
-
-namespace {
-
-// ---- the n best classes per region row on this kernel (wd_topn_similarity_split, include/wedetect_hip_topn.h) ----------------
-// The layout and the scores of p8_best_epilogue: the region row is the LANE (lane & 31), the class the REGISTER, both half-waves hold
-// the same 32 rows of tile i and 32 classes each; every valid element gets the score the materialising epilogue would have stored.
-// Members of P8Retr read here: key [region rows][n_top], cls_offset, list_cap = n_top, scale / bias = the per-row affine (both null: the
-// level affine of p).  A lane reads its row's last slot ONCE (device scope) as the bound, marks which of its 32 keys lie above it
-// (after the first column tiles of a row almost none do, and a wave without one leaves here), then selects the marked keys in
-// descending order — one pass over the 32 registers per key, every index a compile-time constant — and offers the t-th of them to
-// the row at slot t (wd_topn_offer, topn_key.h), reading the bound again in between: the other column tiles of the row raise it.
-// A row with a non-finite accumulator gets NaN score bits in slot 0, as in p8_best_epilogue.
-template <int TM, int TN>
-__device__ __forceinline__ void p8_topn_epilogue(const WdConvGemm& p, const P8Retr& rt, float unscale, int mw, int nw, int lane,
-                                                 const f32x16 (&acc)[TM][TN]) {
-  static_assert(TN * 16 == 32, "one 32-bit mask per (lane, row tile)");
-  if (mw >= p.m || nw >= p.n) return;                              // wave-uniform
-  unsigned long long* key = rt.key;
-  const int n_top = rt.list_cap;
-  const int half = lane >> 5;
-  const int c_lane = nw + 4 * half;                                // class of (j, g, q) = c_lane + 32 j + 8 g + q
-  const unsigned inv0 = 0xFFFFFFFFu - (unsigned)rt.cls_offset - (unsigned)c_lane;
-#pragma unroll
-  for (int i = 0; i < TM; ++i) {
-    if (mw + 32 * i >= p.m) break;                                 // wave-uniform
-    const int m = mw + 32 * i + (lane & 31);
-    const bool row_ok = m < p.m;
-    const int mc = row_ok ? m : p.m - 1;                           // rows past the end: what the padded buffer holds there is not ours to judge
-    EpiRow er = epi_row<true>(p, mc);
-    if (rt.scale) { er.oscale = expf(rt.scale[mc]); er.obias = rt.bias[mc]; }    // wd_topn_affine_score: the same two expressions
-    unsigned long long* slot = key + (size_t)mc * n_top;
-    unsigned long long bound = wd_topn_bound(slot, n_top);
-    unsigned sc[TN * 16];
-    unsigned mask = 0u;
-    bool bad = false;
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int cq = c_lane + 32 * j + 8 * g;
-        if (cq < p.n && row_ok) bad |= wd_any_nonfinite4(acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const unsigned xb = __float_as_uint(p8_score(acc[i][j][4 * g + q], unscale, er));
-          const unsigned long long kq = ((unsigned long long)xb << 32) | (unsigned long long)(inv0 - (unsigned)(32 * j + 8 * g + q));
-          sc[16 * j + 4 * g + q] = xb;
-          mask |= (row_ok && cq + q < p.n && kq > bound) ? (1u << (16 * j + 4 * g + q)) : 0u;
-        }
-      }
-    if (bad) {
-      if (p.range_flag) *p.range_flag = 1u;
-      atomicMax(slot, (0x7FC00000ull << 32) | (unsigned long long)inv0);
-      mask = 0u;
-    }
-    if (__ballot(mask != 0u) == 0ull) continue;                    // wave-uniform: nothing of this group reaches a list
-    unsigned long long prev = ~0ull;
-    for (int t = 0; t < n_top && mask != 0u; ++t) {
-      unsigned long long best = 0ull;
-#pragma unroll
-      for (int e = 0; e < TN * 16; ++e) {
-        const unsigned long long ke = ((unsigned long long)sc[e] << 32) | (unsigned long long)(inv0 - (unsigned)(32 * (e >> 4) + 8 * ((e >> 2) & 3) + (e & 3)));
-        best = (((mask >> e) & 1u) && ke < prev && ke > best) ? ke : best;
-      }
-      if (t > 0) bound = p8_umax64(bound, wd_topn_bound(slot, n_top));
-      if (best <= bound) break;                                    // descending: no later key of this lane is above the bound either
-      wd_topn_offer(slot, n_top, t, best, bound);
-      prev = best;
-    }
-  }
-}
-
-}  // namespace
-
-// wd_topn_similarity_split: the similarity launch with the top-n epilogue (p8_topn_epilogue) in place of the stores; p.c is unused.
-// The caller has checked the sizes (csrc/topn.hip).
 int wd_launch_p8_topn(const WdConvGemm& p, const void* t_split, float unscale, unsigned long long* key, int n_top, int cls_offset,
                       const float* row_scale, const float* row_bias, hipStream_t st) {
-  if (!p8_similarity_ok(p, t_split) || !p.sigmoid || !key || (reinterpret_cast<uintptr_t>(key) & 7u) || n_top < 1 || n_top > 8) return WD_ERR_UNSUPPORTED;
-  P8Retr rt{};
-  rt.scale = row_scale; rt.bias = row_bias;
-  rt.key = key; rt.cls_offset = cls_offset; rt.list_cap = n_top;
-  return launch_p8<P8VAR_TOPN>(p, t_split, unscale, st, nullptr, 0, (p.m + 7) & ~7, (p.n + 7) & ~7, rt);
+  if (!p8_similarity_ok(p, t_split) || !p.sigmoid || !key || (reinterpret_cast<uintptr_t>(key) & 7u) || n_top < 1 || n_top > 8)
+    return WD_ERR_UNSUPPORTED;
+  return launch_p8_padded(p, t_split, unscale, st, P8Topn{key, row_scale, row_bias, cls_offset, n_top});
 }
 
-namespace {
-
-// ---- the best prompt of every class on this kernel (wd_group_similarity_split, include/wedetect_hip_groups.h) -----------------
-// The layout and the scores of p8_best_epilogue: the region row is the LANE (lane & 31), the bank row the REGISTER, and the 32 bank
-// rows nw + 32 j .. + 31 of accumulator tile (i, j) are ONE BIN of the packing (cls_offset and nw are multiples of 32), split
-// between lane L and lane L ^ 32.  Which rows of a bin belong to which class depends on the column only: wave-uniform.
-// Members of P8Retr read here: group_of, bin_first (the whole tables), cls_offset, out [region rows][ldg], n_groups.
-// Per bin (j): the wave reads the bin's classes [g0, g0 + ng) and its 32 group_of words (uniform loads).  The (row, class) pairs
-// of a 32-row tile are dealt in passes of rp = min(32, 64 / ng) rows x ng classes: lane = (row r0 of the pass, class k = lane % ng),
-// the SAME class in every pass, so a lane counts the columns in front of class g0 + k and those of it, (start, ln), once per bin;
-// the longest class of the bin bounds the read loop.
-// Per (i, j): every lane writes its 16 SCORES (p8_score per element: the materialised bits) to the wave's 32 x 36-float patch —
-// the patch of the materialising epilogue, transposed the same way — then, per pass, a lane reads the columns of its class in its
-// row from the patch, four independent reads at a time (a shorter class re-reads its last column: max is idempotent), and stores
-// the maximum at out[row][g0 + k].  Consecutive lanes store consecutive classes of a row: row segments of ng floats, every element
-// written exactly once, no atomics, nothing cleared.  (A first form dealt the pairs 64 per pass with the class changing per
-// pass — a lane exchange and a serial read loop in every pass: 3.53 ms, this form 3.02 ms, against 2.39 ms of the materialising launch on the LVIS
-// plan, profiles/prompt_groups.txt.)  A non-finite accumulator of (row, bin) raises the range flag and turns the row's 32 patch
-// entries into NaN, so every class of the bin gets NaN in that row (fmaxf(NaN, NaN) = NaN).
-// No register is indexed dynamically: i, j, g, q are unrolled, the pass loop touches the patch only.
-template <int TM, int TN>
-__device__ __forceinline__ void p8_group_epilogue(const WdConvGemm& p, const P8Retr& rt, float unscale, int mw, int nw, int lane,
-                                                  const f32x16 (&acc)[TM][TN], float* patch) {
-  if (mw >= p.m || nw >= p.n) return;                              // wave-uniform
-  const int half = lane >> 5, l31 = lane & 31;
-  const float qnan = __uint_as_float(0x7FC00000u);
-#pragma unroll
-  for (int j = 0; j < TN; ++j) {
-    const int c0 = nw + 32 * j;                                    // first bank row of the bin, in this launch
-    if (c0 >= p.n) break;                                          // wave-uniform (p.n is a multiple of 32: a bin is in or out)
-    const int abin = (rt.cls_offset + c0) >> 5;
-    const int g0 = rt.bin_first[abin];
-    int ng = rt.bin_first[abin + 1] - g0;
-    ng = (g0 < 0 || ng < 0) ? 0 : (ng > 32 ? 32 : ng);             // a table that is no plan's: nothing is stored
-    ng = __builtin_amdgcn_readfirstlane(ng);
-    if (ng == 0) continue;
-    // the (row, class) pairs of a pass: rp = min(32, 64 / ng) rows of ng classes; lane = (row r0 of the pass, class k), the same
-    // class in every pass, so its column range is found once per bin
-    const int magic = (65536 + ng - 1) / ng;                       // x / ng = (x * magic) >> 16 for x < 1024, ng <= 32
-    const int rp = ng <= 2 ? 32 : (64 * magic) >> 16;
-    const int r0 = (lane * magic) >> 16;
-    const int k = lane - r0 * ng;
-    const int* __restrict__ go = rt.group_of + rt.cls_offset + c0;
-    const int mine = g0 + k;
-    int start = 0, end = 0, run = 0, maxl = 1, prev = 0;
-#pragma unroll
-    for (int c = 0; c < 32; ++c) {
-      const int gc = go[c];
-      start += gc < mine ? 1 : 0;
-      end += gc <= mine ? 1 : 0;
-      run = (c > 0 && gc == prev) ? run + 1 : 1;
-      maxl = run > maxl ? run : maxl;
-      prev = gc;
-    }
-    maxl = __builtin_amdgcn_readfirstlane(maxl);
-    const int ln = end - start, last = ln > 0 ? ln - 1 : 0;        // columns of class g0 + k: [start, start + ln); ln = 0: a table that is no plan's
-    const bool lane_ok = r0 < rp && ln > 0 && g0 + k < rt.n_groups;
-    const int o1 = last < 1 ? last : 1, o2 = last < 2 ? last : 2, o3 = last < 3 ? last : 3;
-    const int lane_off = (r0 < 32 ? r0 : 0) * EPI_LDT + start;     // start + last <= 31; ln = 0: start <= 32, inside the 36-float pitch
-    float* const outk = rt.out + g0 + k;
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      const int m_first = mw + 32 * i;
-      if (m_first >= p.m) break;                                   // wave-uniform
-      const int m = m_first + l31;
-      const bool row_ok = m < p.m;
-      const EpiRow er = epi_row<true>(p, row_ok ? m : p.m - 1);     // rows past the end: what the padded buffer holds there is not ours to judge
-      bool bad = false;
-#pragma unroll
-      for (int g = 0; g < 4; ++g)
-        bad |= wd_any_nonfinite4(acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]);
-      bad = bad && row_ok;
-      bad = bad || (__shfl_xor((int)bad, 32, 64) != 0);            // the other 16 bank rows of the bin
-      if (bad && p.range_flag) *p.range_flag = 1u;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        f32x4 s;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) s[q] = bad ? qnan : p8_score(acc[i][j][4 * g + q], unscale, er);
-        *reinterpret_cast<f32x4*>(patch + l31 * EPI_LDT + 8 * g + 4 * half) = s;
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      for (int rb = 0; rb < 32; rb += rp) {
-        const int r = rb + r0;                                     // row of the tile
-        const float* src = patch + (r < 32 ? rb : 0) * EPI_LDT + lane_off;
-        // four independent reads (a class of fewer columns re-reads its last one: max is idempotent), then the rare long classes
-        const float v0 = src[0], v1 = src[o1], v2 = src[o2], v3 = src[o3];
-        float v = fmaxf(fmaxf(v0, v1), fmaxf(v2, v3));
-        for (int t = 4; t < maxl; t += 4) {
-          const float w0 = src[t < last ? t : last], w1 = src[t + 1 < last ? t + 1 : last], w2 = src[t + 2 < last ? t + 2 : last],
-                      w3 = src[t + 3 < last ? t + 3 : last];
-          v = fmaxf(v, fmaxf(fmaxf(w0, w1), fmaxf(w2, w3)));
-        }
-        const int mm = m_first + r;
-        if (lane_ok && r < 32 && mm < p.m) outk[(size_t)mm * rt.ldg] = v;
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
-  }
-}
-
-}  // namespace
-
-// wd_group_similarity_split: the similarity launch with the class-max epilogue (p8_group_epilogue) in place of the stores; p.c is
-// unused.  The caller has checked the sizes and the alignment of the tables (csrc/groups.hip); p.n % 32 == 0.
+// p.n % 32 == 0: a bin is in or out of the launch as a whole
 int wd_launch_p8_group(const WdConvGemm& p, const void* t_split, float unscale, const int* group_of, const int* bin_first, int cls_offset,
                        float* out, int ldo, int n_groups, hipStream_t st) {
-  if (!p8_similarity_ok(p, t_split) || !p.sigmoid || !group_of || !bin_first || !out || (p.n & 31) || (cls_offset & 31)) return WD_ERR_UNSUPPORTED;
-  P8Retr rt{};
-  rt.group_of = group_of; rt.bin_first = bin_first;
-  rt.out = out; rt.cls_offset = cls_offset; rt.ldg = ldo; rt.n_groups = n_groups;
-  return launch_p8<P8VAR_GROUP>(p, t_split, unscale, st, nullptr, 0, (p.m + 7) & ~7, p.n, rt);
+  if (!p8_similarity_ok(p, t_split) || !p.sigmoid || !group_of || !bin_first || !out || (p.n & 31) || (cls_offset & 31))
+    return WD_ERR_UNSUPPORTED;
+  return launch_p8_padded(p, t_split, unscale, st, P8Group{group_of, bin_first, out, cls_offset, ldo, n_groups});
 }

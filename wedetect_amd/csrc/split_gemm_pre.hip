@@ -7,6 +7,7 @@
 //   LayerNorm -> 2x2 stride-2 downsample conv.
 #include <cstdlib>
 #include <stdlib.h>
+#include "p8_score_launch.h"
 #include "split_gemm_impl.h"
 
 namespace { constexpr int EPI_RES_DEPTH = 2; }   // residual tiles in flight ahead of the one being stored (ping-pong kernel; the 128 x 128 kernel has registers for one)
@@ -573,13 +574,9 @@ int wd_launch_presplit(const WdConvGemm& p, const void* w, float unscale, int cf
 // wd_retrieval_max with fp16x3 arithmetic: e_split = region embeddings [n_img * rows_per_img, dim] and
 // t_split = text bank [n_cls, dim], both as fp16 hi/lo groups (wd_split_weights; the bank pre-scaled
 // by 1 / t_unscale).  out is zeroed here, then filled by atomic max.  Round 5: on the 256 x 256 kernel with the operand
-// roles swapped (split_gemm_p8.hip: P8Retr) wherever it applies — dim % 32 == 0, aligned scale / bias — in bank chunks of
+// roles swapped (split_gemm_p8.hip: P8RetrMax) wherever it applies — dim % 32 == 0, aligned scale / bias — in bank chunks of
 // 2^20 classes (32-bit DMA offsets); the 256 x 128 ping-pong form below remains for the other shapes and as the A/B
 // reference ($WEDETECT_RETR_P8=0).
-int wd_launch_p8_retrieval(const void* t_split, int n_cls, const void* e_split, int n_rows, int dim, float unscale,
-                           const float* scale, const float* bias, const int* count, int rows_per_img, float* out, int ldo,
-                           unsigned* range_flag, hipStream_t st);   // split_gemm_p8.hip
-
 extern "C" int wd_retrieval_max_split(const void* e_split, const void* t_split, float t_unscale, const float* scale,
                                       const float* bias, const int32_t* count, float* out, int32_t n_img,
                                       int32_t rows_per_img, int32_t n_cls, int32_t dim, uint32_t* range_flag, void* stream) {
@@ -618,8 +615,6 @@ extern "C" int wd_retrieval_max_split(const void* e_split, const void* t_split, 
   const RetrArgs ra{scale, bias, count, out, rows_per_img, n_cls};
   return launch_pingpong<SVAR_RETRMAX, 3, 2>(p, t_split, t_unscale, st, ra);
 }
-
-int wd_launch_p8_similarity(const WdConvGemm& p, const void* t_split, float unscale, hipStream_t st);   // split_gemm_p8.hip
 
 // wd_similarity_split (ABI 14): the region x text similarity GEMM on the fp16x3 256 x 256 kernel.
 extern "C" int wd_similarity_split(const void* e_split, int64_t rows, const void* t_split, float unscale, float* out, int32_t n_cls,

@@ -3,12 +3,9 @@
 //   wd_topn_rows               the same merge from a materialised block of scores or raw logits: one wave per row
 //   wd_topn_unpack             one slot of every row -> (score, label)
 //   wd_topn_kept               the lists of the rows NMS kept
-#include "common.h"
+#include "p8_score_launch.h"
 #include "topn_key.h"
 #include "wedetect_hip_topn.h"
-
-int wd_launch_p8_topn(const WdConvGemm& p, const void* t_split, float unscale, unsigned long long* key, int n_top, int cls_offset,
-                      const float* row_scale, const float* row_bias, hipStream_t st);   // split_gemm_p8.hip
 
 namespace {
 
@@ -103,7 +100,7 @@ extern "C" int wd_topn_similarity_split(const void* e_split, int64_t rows, const
   if (!topn_key_ok(key, n_top, rows, cls_offset, n_cls)) return WD_ERR_BAD_ARG;
   if ((row_scale == nullptr) != (row_bias == nullptr) || (row_scale && seg_rows > 0)) return WD_ERR_BAD_ARG;
   if (row_scale && ((reinterpret_cast<uintptr_t>(row_scale) | reinterpret_cast<uintptr_t>(row_bias)) & 3u)) return WD_ERR_BAD_ARG;
-  if ((unsigned long long)((n_cls + 7) & ~7) * (unsigned long long)((dim + 15) / 16 * 16) * 4ull >= (1ull << 32)) return WD_ERR_UNSUPPORTED;
+  if (!wd_similarity_bank_fits(n_cls, dim)) return WD_ERR_UNSUPPORTED;
   return wd_launch_p8_topn(p, t_split, unscale, reinterpret_cast<unsigned long long*>(key), n_top, cls_offset, row_scale, row_bias,
                            static_cast<hipStream_t>(stream));
 }
