@@ -219,6 +219,7 @@ SIZES = [(50, 61), (64, 47), (39, 64)]                       # (h, w) of the ima
 
 def _tta_pipeline(scales, directions=("horizontal",)):
     """mmyolo's TTA pipeline shape: resize branches x flip branches x PackDetInputs."""
+    from wedetect_amd import tta  # noqa: F401  (registers TestTimeAug / RandomFlip: this file also runs on its own)
     from wedetect_amd.pipeline import Compose
     resize = [dict(type="Compose", transforms=[dict(type="WeDetectKeepRatioResize", scale=(s, s)),
                                                dict(type="WeDetectLetterResize", scale=(s, s), allow_scale_up=False, pad_val=dict(img=114))])

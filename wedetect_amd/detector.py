@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 from .arch import EMBED_DIM, all_params, get_arch
+from .guarded import Blob, merged_parts, run_steps
 from .registry import MODELS
 
 _IMG_SIZE = {"tiny": (640, 640), "base": (640, 640), "large": (1280, 1280), "nano": (128, 128)}
@@ -235,6 +236,23 @@ class _TowerHolder:
                 raise RuntimeError("tower buffers were re-allocated during graph capture")
         return g(images_u8, text, meta)
 
+    def checked_step(self, tower, images_u8, text, meta, text_counts=None, **kw):
+        """The in-line step: ``detect``, then the step's counts through ``ImageTower.checked_counts`` — one D2H sync per
+        batch and the fp16x3 range guard, which may recalibrate, repeat the step or fall back to fp32 — then the holder's
+        precision follows the tower.  Returns (the tower's result buffers, counts list)."""
+        run = lambda: self.detect(tower, images_u8, text, meta, text_counts=text_counts, **kw)
+        res = run()
+        recal = (lambda: self.recalibrate(tower, images_u8)) if self.auto_calibrate else None
+        counts = tower.checked_counts(res, run, recal)
+        # towers built later for other shapes start in fp32 too while this one is in its fallback (round 6: not for good — after
+        # ImageTower.FALLBACK_RETRY clean batches it re-calibrates and returns to fp16x3, and so does the holder's default)
+        self.precision = "fp32" if tower.overflowed else self._asked_precision
+        return res, counts
+
+    def inline_only(self) -> bool:
+        """True while a tower is in its fp32 fallback: every step then goes in line (wedetect_amd/guarded.py)."""
+        return any(t.overflowed for t in self._towers.values())
+
 
 class _DeviceModule(torch.nn.Module):
     """nn.Module plumbing shared by the two detectors: no parameters, weights in ``self._h`` (a _TowerHolder)."""
@@ -369,14 +387,8 @@ class SimpleYOLOWorldDetector(_DeviceModule):
         # torchvision.ops.batched_nms(bbox, scores, labels, 0.7)[:num_proposals] (generate_proposal.py:1210), with the
         # branch threshold of the device the reference's tensors would live on ($WEDETECT_TV_NMS_DEVICE: "cpu" = the CPU
         # reference path the parity contract names, "cuda" = what the script's hard-coded .cuda() run takes)
-        run = lambda: self._h.detect(tower, x, tower.P["prompts"], meta, normalize_text=False, score_thr=0.0, with_embed=True,
-                                     nms="torchvision", nms_param=self.tv_trick_max_numel, nms_device=self.tv_nms_device)
-        res = run()
-        recal = (lambda: self._h.recalibrate(tower, x)) if self._h.auto_calibrate else None
-        counts = tower.checked_counts(res, run, recal)      # one D2H sync per batch (+ the fp16x3 range guard)
-        # towers built later for other shapes start in fp32 too while this one is in its fallback (round 6: not for good — after
-        # ImageTower.FALLBACK_RETRY clean batches it re-calibrates and returns to fp16x3, and so does the holder's default)
-        self._h.precision = "fp32" if tower.overflowed else self._h._asked_precision
+        res, counts = self._h.checked_step(tower, x, tower.P["prompts"], meta, normalize_text=False, score_thr=0.0, with_embed=True,
+                                           nms="torchvision", nms_param=self.tv_trick_max_numel, nms_device=self.tv_nms_device)
         return res, counts, tower
 
     def predict_stream(self, images_or_paths: Sequence[Union[str, object]], batch_size: int, *, rescale: bool = True,
@@ -541,6 +553,48 @@ def _meta_of(sample) -> dict:
     if isinstance(sample, dict):
         return sample.get("metainfo", sample)
     return getattr(sample, "metainfo", {}) or {}
+
+
+def _as_sample(sample) -> DetDataSample:
+    """``None`` / a dict (its ``metainfo``) / a data sample -> the data sample that takes the predictions."""
+    if sample is None:
+        return DetDataSample()
+    return DetDataSample(metainfo=_meta_of(sample)) if isinstance(sample, dict) else sample
+
+
+def _batch_hw(xs: Sequence[torch.Tensor], what: str = "") -> Tuple[int, int]:
+    """(H, W) of a batch of [3, H, W] inputs of one shape, H and W multiples of 32; ``what`` prefixes the error texts."""
+    shapes = {tuple(t.shape) for t in xs}
+    if len(shapes) != 1 or len(next(iter(shapes))) != 3 or next(iter(shapes))[0] != 3:
+        raise ValueError(f"{what}inputs must be [3, H, W] tensors of one shape after the test pipeline, got {sorted(shapes)}")
+    _, hh, ww = next(iter(shapes))
+    if hh % 32 or ww % 32:
+        raise ValueError(f"{what}input size {hh}x{ww} is not a multiple of 32 (letterbox to img_scale first)")
+    return int(hh), int(ww)
+
+
+def _nhwc_u8(xs: Sequence[torch.Tensor], dev, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """A checked batch (``_batch_hw``) of BGR [3, H, W] inputs -> the tower's RGB NHWC uint8 batch on ``dev``, written into
+    ``out`` when given: bgr_to_rgb + NHWC (data_preprocessor.py:35-36)."""
+    from . import lib as L
+    chw = torch.stack([x.to(dev) for x in xs])               # [b, 3, H, W] BGR, contiguous
+    if chw.dtype not in (torch.uint8, torch.float32):
+        chw = chw.to(torch.float32)
+    if out is None:
+        out = torch.empty(chw.shape[0], chw.shape[2], chw.shape[3], 3, dtype=torch.uint8, device=dev)
+    L.chw_to_hwc_u8(chw, out)
+    return out
+
+
+def _tiled_ctl_parts(total: int) -> tuple:
+    """The control block of ``predict_tiled`` (guarded.layout): the tile descriptors, then the per-tile metadata."""
+    from .tiling import TILE_DTYPE
+    return (("plan", (total * TILE_DTYPE.itemsize,), torch.uint8), ("meta", (total, 8), torch.float32))
+
+
+def _views_ctl_parts(V: int, B: int) -> tuple:
+    """The control block of ``predict_views`` (guarded.layout): flip codes, image sizes, per-view metadata."""
+    return (("flip", (V,), torch.int32), ("wh", (B, 2), torch.float32), ("meta", (V, B, 8), torch.float32))
 
 
 def _flat_texts(texts) -> Tuple[str, ...]:
@@ -876,61 +930,32 @@ class YOLOWorldDetector(_DeviceModule):
         if len(samples) != len(xs):
             raise ValueError(f"{len(xs)} inputs but {len(samples)} data samples")
         banks = [self._bank_for(s) for s in samples]
-        shapes = {tuple(t.shape) for t in xs}
-        if len(shapes) != 1 or len(next(iter(shapes))) != 3 or next(iter(shapes))[0] != 3:
-            raise ValueError(f"inputs must be [3, H, W] tensors of one shape after the test pipeline, got {sorted(shapes)}")
-        _, hh, ww = next(iter(shapes))
-        if hh % 32 or ww % 32:
-            raise ValueError(f"input size {hh}x{ww} is not a multiple of 32 (letterbox to img_scale first)")
-        out: List[Optional[DetDataSample]] = [None] * len(xs)
+        hh, ww = _batch_hw(xs)
         # ONE tower step for the batch, whatever the samples' class lists: one bank object for all -> the shared-bank step;
         # otherwise the banks travel as [b, k_max, 768] + device counts and every image is scored against its own
         # (yolo_world.py:94-96: ``texts = [data_sample.texts for data_sample in batch_data_samples]``)
-        from . import lib as L
-        idxs = list(range(len(xs)))
         packed = self._packed_for(banks, dev)
-        groups_kw = {}
+        kw = self._step_kw(modes=True)
         if self.prompt_groups:
             if packed is not None:
                 raise NotImplementedError("prompt_groups=True with differing class lists in one batch is not implemented (one "
                                           "packing plan per step); batch images of one class list")
-            groups_kw = dict(prompt_groups=self._plan_for(samples[0]))
-        chw = torch.stack([xs[i].to(dev) for i in idxs])     # [b, 3, H, W] BGR, contiguous
-        if chw.dtype not in (torch.uint8, torch.float32):
-            chw = chw.to(torch.float32)
-        x = torch.empty(len(idxs), hh, ww, 3, dtype=torch.uint8, device=dev)
-        L.chw_to_hwc_u8(chw, x)                              # bgr_to_rgb + NHWC (data_preprocessor.py:35-36)
-        metas = []
-        for i in idxs:
-            metas.append(letterbox_meta(_meta_of(samples[i]), hh, ww, rescale))
-        tower = self._h.tower(len(idxs), hh, ww)
-        meta = torch.tensor(metas, dtype=torch.float32, device=dev)
-        if packed is None:
-            bank, counts_dev = banks[0].to(dev), None
-        else:
-            bank, counts_dev = packed
-        run = lambda: self._h.detect(tower, x, bank, meta, text_counts=counts_dev, normalize_text=True, score_thr=self.test_cfg["score_thr"],
-                                     iou_thr=self.test_cfg["nms"]["iou_threshold"], with_embed=False,
-                                     # mmdet _bbox_post_process -> mmcv.ops.batched_nms(bboxes, scores, labels, cfg.nms)
-                                     nms="mmcv", nms_param=int(self.test_cfg["nms"].get("split_thr", 10000)), **self._best_kw(),
-                                     **self._sparse_kw(), **(dict(top_names=self.top_names) if self.top_names else {}), **groups_kw)
-        res = run()
-        recal = (lambda: self._h.recalibrate(tower, x)) if self._h.auto_calibrate else None
-        counts = tower.checked_counts(res, run, recal)
-        self._h.precision = "fp32" if tower.overflowed else self._h._asked_precision
-        for j, (i, n) in enumerate(zip(idxs, counts)):
+            kw["prompt_groups"] = self._plan_for(samples[0])
+        x = _nhwc_u8(xs, dev)
+        tower = self._h.tower(len(xs), hh, ww)
+        meta = torch.tensor([letterbox_meta(_meta_of(s), hh, ww, rescale) for s in samples], dtype=torch.float32, device=dev)
+        bank, counts_dev = (banks[0].to(dev), None) if packed is None else packed
+        res, counts = self._h.checked_step(tower, x, bank, meta, text_counts=counts_dev, **kw)
+        out = []
+        for j, n in enumerate(counts):
             inst = InstanceData(bboxes=res["bboxes"][j, :n].clone(), scores=res["scores"][j, :n].clone(),
                                 labels=res["labels"][j, :n].to(torch.int64))
             if self.top_names:
                 inst.top_labels = res["top_labels"][j, :n].to(torch.int64)
                 inst.top_scores = res["top_scores"][j, :n].clone()
-            s = samples[i]
-            if s is None:
-                s = DetDataSample()
-            elif isinstance(s, dict):
-                s = DetDataSample(metainfo=_meta_of(s))
+            s = _as_sample(samples[j])
             s.pred_instances = inst
-            out[i] = s
+            out.append(s)
         return out
 
     def predict_stream(self, data_infos: Sequence[dict], batch_size: int, pipeline_cfg, *, rescale: bool = True,
@@ -979,10 +1004,16 @@ class YOLOWorldDetector(_DeviceModule):
             raise NotImplementedError(f"{what} with sparse_scores=True is not implemented (its packed result blobs do not carry "
                                       "the sparse status; use predict)")
 
-    def _step_kw(self) -> dict:
+    def _step_kw(self, modes: bool = False) -> dict:
+        """The keywords of this detector's tower steps (mmdet ``_bbox_post_process`` -> ``mmcv.ops.batched_nms(bboxes, scores,
+        labels, cfg.nms)``).  ``modes``: with the keywords of the modes that are ON (``predict``; the plan of prompt groups
+        belongs to a bank and is added there) — a mode that is off adds nothing, so graph keys stay as they were."""
         cfg = self.test_cfg
-        return dict(normalize_text=True, score_thr=cfg["score_thr"], iou_thr=cfg["nms"]["iou_threshold"], with_embed=False,
-                    nms="mmcv", nms_param=int(cfg["nms"].get("split_thr", 10000)))
+        kw = dict(normalize_text=True, score_thr=cfg["score_thr"], iou_thr=cfg["nms"]["iou_threshold"], with_embed=False,
+                  nms="mmcv", nms_param=int(cfg["nms"].get("split_thr", 10000)))
+        if modes:
+            kw.update(self._best_kw(), **self._sparse_kw(), **(dict(top_names=self.top_names) if self.top_names else {}))
+        return kw
 
     @torch.no_grad()
     def predict_tiled(self, image, texts=None, *, tile=None, overlap: float = 0.2, overview: bool = True, tile_batch: int = 32,
@@ -1005,10 +1036,9 @@ class YOLOWorldDetector(_DeviceModule):
 
         The pipelined steps only DETECT a trip of the fp16x3 range guard (a flag, or a count of -1, arrives with the
         download); the image is then run again step by step in line through ``checked_counts``, which owns the guard's logic,
-        as wedetect_amd/stream.py does.  Returns a ``DetDataSample`` whose ``pred_instances`` holds HOST tensors: ``bboxes``
+        the protocol of wedetect_amd/guarded.py.  Returns a ``DetDataSample`` whose ``pred_instances`` holds HOST tensors: ``bboxes``
         (image pixels), ``scores``, ``labels`` and ``tiles`` (the plan index of the tile each row came from)."""
         self._refuse_best("predict_tiled")
-        from . import lib as L
         from . import tile as T
         from . import tiling as G
         from .pipeline import cv_resize_pad
@@ -1046,103 +1076,51 @@ class YOLOWorldDetector(_DeviceModule):
             sample.set_metainfo(dict(scale_factor=g["scale_factor"], pad_param=g["pad_param"], img_shape=(th, tw, 3)))
             return self.predict([canvas.permute(2, 0, 1).contiguous()], [sample])[0]          # predict takes CHW BGR
         h = self._h
-        steps = G.step_sizes(len(plan), tile_batch)
-        total = sum(b for _, b in steps)
+        sizes = G.step_sizes(len(plan), tile_batch)
+        total = sum(b for _, b in sizes)
         max_in = h.max_out
         if total * max_in > T.MERGE_MAX_ROWS:
             raise NotImplementedError(f"{total} tiles x {max_in} rows per tile exceed the merge's {T.MERGE_MAX_ROWS} rows: use larger "
                                       "tiles, less overlap or a smaller test_cfg.max_per_img")
         plan_p = G.pad_plan(plan, total)
         og = G.overview_geometry(H, W, (th, tw)) if bool((plan["kind"] == G.OVERVIEW).any()) else None
-        meta_host = G.tile_meta(plan_p, (th, tw), None if og is None else og["meta"])
+        B = self._tiled_buffers(total, max_in, th, tw, max_out, len(sizes), dev)
         # ONE control block: descriptors, then the per-tile metadata at a 256-byte boundary
-        meta_off = (total * T.TILE_DTYPE.itemsize + 255) // 256 * 256
-        B = self._tiled_buffers(total, max_in, th, tw, max_out, len(steps), dev)
-        ctl_np = B["ctl_pin"].numpy()                        # the previous call ended with a synchronisation: free to rewrite
-        ctl_np[: total * T.TILE_DTYPE.itemsize] = plan_p.view(np.uint8)
-        ctl_np[meta_off: meta_off + total * 32] = meta_host.view(np.uint8).reshape(-1)
-        ctl = B["ctl"]
-        ctl.copy_(B["ctl_pin"], non_blocking=True)
-        meta = ctl[meta_off: meta_off + total * 32].view(torch.float32).view(total, 8)
-        tiles = B["tiles"]
+        ctl_host = B["ctl_io"].host                          # the previous call ended with a synchronisation: free to rewrite
+        ctl_host["plan"].numpy()[:] = plan_p.view(np.uint8)
+        ctl_host["meta"].numpy()[:] = G.tile_meta(plan_p, (th, tw), None if og is None else og["meta"])
+        B["ctl_io"].upload()
+        ctl, meta, tiles = B["ctl"], B["ctl_io"].views["meta"], B["tiles"]
         T.tile_cut_u8(img_dev, ctl.data_ptr(), plan_p, tiles, fill=114, swap_rb=swap)
         if og is not None:
             k = int(np.nonzero(plan_p["kind"] == G.OVERVIEW)[0][0])
             cv_resize_pad(img_dev, og["dh"], og["dw"], og["interp"], (th, tw), og["top"], og["left"], og["pad_val"], swap_rb=swap,
                           out=tiles[k])
-        kw = self._step_kw()
         n_cls = int(bank.shape[0])
         split_thr = int(self.test_cfg["nms"].get("split_thr", 10000))
-        towers = [h.tower(b, th, tw) for _, b in steps]
-        main = torch.cuda.current_stream()
-
-        def stack(res, tower, i, lo, b):
-            B["boxes"][lo:lo + b].copy_(res["bboxes"], non_blocking=True)
-            B["scores"][lo:lo + b].copy_(res["scores"], non_blocking=True)
-            B["labels"][lo:lo + b].copy_(res["labels"], non_blocking=True)
-            B["counts"][lo:lo + b].copy_(res["count"], non_blocking=True)
-            B["flags"][i].copy_(tower.step_range_flags, non_blocking=True)
+        steps, lo = [], 0
+        for i, (_, b) in enumerate(sizes):                   # destination: the step's flag row and its rows of the stacked buffers
+            steps.append((h.tower(b, th, tw), tiles[lo:lo + b], bank, None, meta[lo:lo + b], i, slice(lo, lo + b)))
+            lo += b
 
         def merge_and_download():
             T.tile_merge(B["boxes"], B["scores"], B["labels"], B["counts"], ctl.data_ptr(), total, max_in, n_cls, float(edge_margin),
                          iou, split_thr, max_out, B["out_boxes"], B["out_scores"], B["out_labels"], B["out_src"], B["out_count"], B["ws"])
-            B["pin"].copy_(B["stage"], non_blocking=True)    # ONE packed D2H: rows, count, range flags
-            torch.cuda.current_stream().synchronize()
             if stats is not None:
                 stats["d2h_copies"] += 1
-            return {k: v.clone() for k, v in B["host"].items()}
+            return B["out_io"].fetch()                       # ONE packed D2H: rows, count, range flags
 
-        inline = any(t.overflowed for t in h._towers.values())       # a tower in its fp32 fallback: every step goes in line
-        host = None
-        if not inline:
-            lo = 0
-            for i, ((_, b), tower) in enumerate(zip(steps, towers)):
-                x = tiles[lo:lo + b]
-                h.calibrate_first(tower, x)
-                res = tower.detect(x, bank, meta[lo:lo + b], overlap_post=True, **kw)
-                with torch.cuda.stream(tower.post_stream):   # before the next post-process overwrites the tower's rows
-                    stack(res, tower, i, lo, b)
-                    B["events"][i].record(tower.post_stream)
-                lo += b
-            for i in range(len(steps)):
-                main.wait_event(B["events"][i])
-            host = merge_and_download()
-            if stats is not None:
-                stats["steps"] += len(steps)
-            fl = [f for (tower, row) in zip(towers, host["flags"].tolist()) if tower.precision == "fp16x3" for f in row]
-            if int(host["count"]) < 0 or any(fl):
-                inline = True
-                if stats is not None:
-                    stats["trips"] += 1
-        if inline:
-            torch.cuda.synchronize(dev)
-            for tower in set(towers):
-                tower.clear_range_flags()                    # a discarded step may have raised them
-            lo = 0
-            for i, ((_, b), tower) in enumerate(zip(steps, towers)):
-                x, m = tiles[lo:lo + b], meta[lo:lo + b]
-                run = lambda: h.detect(tower, x, bank, m, **kw)
-                res = run()
-                recal = (lambda: h.recalibrate(tower, x)) if h.auto_calibrate else None
-                tower.checked_counts(res, run, recal)
-                h.precision = "fp32" if tower.overflowed else h._asked_precision
-                stack(res, tower, i, lo, b)
-                lo += b
-            B["flags"].zero_()
-            host = merge_and_download()
-            if stats is not None:
-                stats["steps"] += len(steps)
-                stats["inline"] = True
-            if int(host["count"]) < 0:
-                raise RuntimeError("non-finite scores survived the in-line range guard")
-        n = int(host["count"])
-        sample.pred_instances = InstanceData(bboxes=host["boxes"][:n], scores=host["scores"][:n], labels=host["labels"][:n].to(torch.int64),
-                                             tiles=(host["src"][:n] // max_in).to(torch.int64))
+        host = run_steps(h, steps, self._step_kw(), B, merge_and_download, stats)
+        n = int(host["out_count"])
+        sample.pred_instances = InstanceData(bboxes=host["out_boxes"][:n], scores=host["out_scores"][:n],
+                                             labels=host["out_labels"][:n].to(torch.int64),
+                                             tiles=(host["out_src"][:n] // max_in).to(torch.int64))
         return sample
 
     def _tiled_buffers(self, total: int, max_in: int, th: int, tw: int, max_out: int, n_steps: int, dev) -> dict:
         """Device buffers of ``predict_tiled`` for one geometry, kept between calls: the tiles, the stacked per-tile rows, the
-        merge's workspace, and ONE staging blob (merged rows, count, range flags per step) with its pinned twin."""
+        merge's workspace, ONE control block (``ctl_io``: descriptors, per-tile metadata) and ONE staging blob (``out_io``:
+        merged rows, count, range flags per step), each a ``guarded.Blob`` whose device parts are entries of their own."""
         from . import tile as T
         key = (total, max_in, th, tw, max_out, n_steps, str(dev))
         B = getattr(self, "_tiled", None)
@@ -1153,21 +1131,8 @@ class YOLOWorldDetector(_DeviceModule):
         B = dict(key=key, tiles=e(total, th, tw, 3, dt=u8), boxes=e(total, max_in, 4), scores=e(total, max_in),
                  labels=e(total, max_in, dt=i32), counts=e(total, dt=i32),
                  ws=e(T.merge_workspace_bytes(total, max_in), dt=u8), events=[torch.cuda.Event() for _ in range(n_steps)])
-        ctl_bytes = (total * T.TILE_DTYPE.itemsize + 255) // 256 * 256 + total * 32      # descriptors | per-tile metadata
-        B["ctl"], B["ctl_pin"] = e(ctl_bytes, dt=u8), torch.zeros(ctl_bytes, dtype=u8).pin_memory()
-        parts = (("boxes", (max_out, 4), f32), ("scores", (max_out,), f32), ("labels", (max_out,), i32), ("src", (max_out,), i32),
-                 ("count", (1,), i32), ("flags", (n_steps, 2), i32))
-        off, lay = 0, []
-        for name, shape, dt in parts:
-            nb = int(np.prod(shape)) * 4
-            lay.append((name, shape, dt, off, nb))
-            off += (nb + 255) // 256 * 256
-        B["stage"] = torch.zeros(off, dtype=u8, device=dev)
-        B["pin"] = torch.zeros(off, dtype=u8).pin_memory()
-        B["host"] = {}
-        for name, shape, dt, o, nb in lay:
-            B["out_" + name if name != "flags" else "flags"] = B["stage"][o:o + nb].view(dt).view(shape)
-            B["host"][name] = B["pin"][o:o + nb].view(dt).view(shape)
+        B["ctl_io"], B["out_io"] = Blob(_tiled_ctl_parts(total), dev), Blob(merged_parts(max_out, n_steps), dev)
+        B.update(B["out_io"].views, ctl=B["ctl_io"].dev, stage=B["out_io"].dev)
         self._tiled = B
         return B
 
@@ -1184,12 +1149,11 @@ class YOLOWorldDetector(_DeviceModule):
             included; each step's rows are copied into stacked [V, B, max_in] buffers on the post stream) -> ONE merge
             (``wd_views_merge``: un-flip, sort, mmcv-form NMS per image over all views) -> ONE download (rows, counts, flags)
 
-        The pipelined steps only DETECT a trip of the fp16x3 range guard, as in ``predict_tiled``: the views are then run again
+        The pipelined steps only DETECT a trip of the fp16x3 range guard (wedetect_amd/guarded.py): the views are then run again
         in line through ``checked_counts`` and merged again.  Returns the FIRST view's sample of every image (mmdet
         ``_merge_single_sample``); ``pred_instances`` holds HOST tensors: ``bboxes`` (original-image pixels), ``scores``,
         ``labels`` and ``views`` (the view each row came from)."""
         self._refuse_best("predict_views")
-        from . import lib as L
         from . import views as VW
         from .tta import check_tta_cfg
         h = self._h
@@ -1210,13 +1174,7 @@ class YOLOWorldDetector(_DeviceModule):
         for v, (xs, samples) in enumerate(views):
             if len(xs) != B or len(samples) != B or B < 1:
                 raise ValueError(f"view {v}: {len(xs)} inputs and {len(samples)} data samples, but view 0 has {B} images")
-            shp = {tuple(t.shape) for t in xs}
-            if len(shp) != 1 or len(next(iter(shp))) != 3 or next(iter(shp))[0] != 3:
-                raise ValueError(f"view {v}: inputs must be [3, H, W] tensors of one shape after the test pipeline, got {sorted(shp)}")
-            _, hh, ww = next(iter(shp))
-            if hh % 32 or ww % 32:
-                raise ValueError(f"view {v}: input size {hh}x{ww} is not a multiple of 32 (letterbox to img_scale first)")
-            shapes.append((int(hh), int(ww)))
+            shapes.append(_batch_hw(xs, f"view {v}: "))
             codes = set()
             for s in samples:
                 m = _meta_of(s)
@@ -1233,7 +1191,7 @@ class YOLOWorldDetector(_DeviceModule):
         n_cls = max(int(b.shape[0]) for banks in banks_v for b in banks)
         iou, split_thr = cfg["nms"]["iou_threshold"], int(cfg["nms"].get("split_thr", 10000))
         Bf = self._views_buffers(V, B, max_in, max_out, tuple(shapes), dev)
-        ctl = Bf["ctl_host"]                                 # the previous call ended with a synchronisation: free to rewrite
+        ctl = Bf["ctl_io"].host                              # the previous call ended with a synchronisation: free to rewrite
         ctl["flip"][:] = torch.tensor(flips, dtype=torch.int32)
         for b, s in enumerate(views[0][1]):
             ori = _meta_of(s).get("ori_shape", shapes[0])
@@ -1241,92 +1199,39 @@ class YOLOWorldDetector(_DeviceModule):
         for v, (_, samples) in enumerate(views):
             ctl["meta"][v] = torch.tensor([letterbox_meta(_meta_of(s), shapes[v][0], shapes[v][1], rescale) for s in samples],
                                           dtype=torch.float32)
-        Bf["ctl"].copy_(Bf["ctl_pin"], non_blocking=True)
-        kw = self._step_kw()
+        Bf["ctl_io"].upload()
         towers = [h.tower(B, hh, ww) for hh, ww in shapes]
         packed = [self._packed_for(banks, dev) for banks in banks_v]
         text = [(banks[0].to(dev), None) if p is None else p for banks, p in zip(banks_v, packed)]
         for v, (xs, _) in enumerate(views):
-            chw = torch.stack([x.to(dev) for x in xs])       # [B, 3, H, W] BGR, contiguous
-            if chw.dtype not in (torch.uint8, torch.float32):
-                chw = chw.to(torch.float32)
-            L.chw_to_hwc_u8(chw, Bf["x"][v])                 # bgr_to_rgb + NHWC, as predict
-        main = torch.cuda.current_stream()
+            _nhwc_u8(xs, dev, out=Bf["x"][v])                # as predict
         if stats is not None:
             stats.update(views=V, steps=0, trips=0, inline=False, d2h_copies=0)
-
-        def stack(res, tower, v):
-            Bf["boxes"][v].copy_(res["bboxes"], non_blocking=True)
-            Bf["scores"][v].copy_(res["scores"], non_blocking=True)
-            Bf["labels"][v].copy_(res["labels"], non_blocking=True)
-            Bf["counts"][v].copy_(res["count"], non_blocking=True)
-            Bf["flags"][v].copy_(tower.step_range_flags, non_blocking=True)
+        steps = [(towers[v], Bf["x"][v], text[v][0], text[v][1], Bf["meta"][v], v, v) for v in range(V)]
 
         def merge_and_download():
             VW.views_merge(Bf["boxes"], Bf["scores"], Bf["labels"], Bf["counts"], Bf["flip"], Bf["wh"], V, B, max_in, n_cls, iou, split_thr,
                            max_out, Bf["out_boxes"], Bf["out_scores"], Bf["out_labels"], Bf["out_src"], Bf["out_count"], Bf["ws"])
-            Bf["pin"].copy_(Bf["stage"], non_blocking=True)  # ONE packed D2H: rows, counts, range flags
-            torch.cuda.current_stream().synchronize()
             if stats is not None:
                 stats["d2h_copies"] += 1
-            return {k: t.clone() for k, t in Bf["host"].items()}
+            return Bf["out_io"].fetch()                      # ONE packed D2H: rows, counts, range flags
 
-        inline = any(t.overflowed for t in h._towers.values())       # a tower in its fp32 fallback: every step goes in line
-        host = None
-        if not inline:
-            for v, tower in enumerate(towers):
-                x = Bf["x"][v]
-                h.calibrate_first(tower, x)
-                res = tower.detect(x, text[v][0], Bf["meta"][v], overlap_post=True, text_counts=text[v][1], **kw)
-                with torch.cuda.stream(tower.post_stream):   # before the next post-process overwrites the tower's rows
-                    stack(res, tower, v)
-                    Bf["events"][v].record(tower.post_stream)
-            for v in range(V):
-                main.wait_event(Bf["events"][v])
-            host = merge_and_download()
-            if stats is not None:
-                stats["steps"] += V
-            fl = [f for (tower, row) in zip(towers, host["flags"].tolist()) if tower.precision == "fp16x3" for f in row]
-            if int(host["count"].min()) < 0 or any(fl):
-                inline = True
-                if stats is not None:
-                    stats["trips"] += 1
-        if inline:
-            torch.cuda.synchronize(dev)
-            for tower in set(towers):
-                tower.clear_range_flags()                    # a discarded step may have raised them
-            for v, tower in enumerate(towers):
-                x, m, (bank, counts_dev) = Bf["x"][v], Bf["meta"][v], text[v]
-                run = lambda: h.detect(tower, x, bank, m, text_counts=counts_dev, **kw)
-                res = run()
-                recal = (lambda: h.recalibrate(tower, x)) if h.auto_calibrate else None
-                tower.checked_counts(res, run, recal)
-                h.precision = "fp32" if tower.overflowed else h._asked_precision
-                stack(res, tower, v)
-            Bf["flags"].zero_()
-            host = merge_and_download()
-            if stats is not None:
-                stats["steps"] += V
-                stats["inline"] = True
-            if int(host["count"].min()) < 0:
-                raise RuntimeError("non-finite scores survived the in-line range guard")
+        host = run_steps(h, steps, self._step_kw(), Bf, merge_and_download, stats)
         out = []
         for b, s in enumerate(views[0][1]):
-            n = int(host["count"][b])
-            if s is None:
-                s = DetDataSample()
-            elif isinstance(s, dict):
-                s = DetDataSample(metainfo=_meta_of(s))
-            s.pred_instances = InstanceData(bboxes=host["boxes"][b, :n], scores=host["scores"][b, :n],
-                                            labels=host["labels"][b, :n].to(torch.int64),
-                                            views=(host["src"][b, :n] // max_in).to(torch.int64))
+            n = int(host["out_count"][b])
+            s = _as_sample(s)
+            s.pred_instances = InstanceData(bboxes=host["out_boxes"][b, :n], scores=host["out_scores"][b, :n],
+                                            labels=host["out_labels"][b, :n].to(torch.int64),
+                                            views=(host["out_src"][b, :n] // max_in).to(torch.int64))
             out.append(s)
         return out
 
     def _views_buffers(self, V: int, B: int, max_in: int, max_out: int, shapes: tuple, dev) -> dict:
         """Device buffers of ``predict_views`` for one geometry, kept between calls: the NHWC input of every view, the stacked
-        per-view rows, ONE control block (flip codes, image sizes, per-view metadata) with its pinned twin, the merge's
-        workspace, and ONE staging blob (merged rows, counts, range flags per view) with its pinned twin."""
+        per-view rows, the merge's workspace, ONE control block (``ctl_io``: flip codes, image sizes, per-view metadata) and ONE
+        staging blob (``out_io``: merged rows, counts, range flags per view), each a ``guarded.Blob`` whose device parts are
+        entries of their own."""
         from . import views as VW
         key = (V, B, max_in, max_out, shapes, str(dev))
         Bf = getattr(self, "_views", None)
@@ -1334,28 +1239,11 @@ class YOLOWorldDetector(_DeviceModule):
             return Bf
         f32, i32, u8 = torch.float32, torch.int32, torch.uint8
         e = lambda *s, dt=f32: torch.empty(*s, dtype=dt, device=dev)
-
-        def blob(parts):
-            off, lay = 0, []
-            for name, shape, dt in parts:
-                nb = int(np.prod(shape)) * 4
-                lay.append((name, shape, dt, off, nb))
-                off += (nb + 255) // 256 * 256
-            return off, lay
         Bf = dict(key=key, x=[e(B, hh, ww, 3, dt=u8) for hh, ww in shapes], boxes=e(V, B, max_in, 4), scores=e(V, B, max_in),
                   labels=e(V, B, max_in, dt=i32), counts=e(V, B, dt=i32), ws=e(VW.merge_workspace_bytes(V, B, max_in), dt=u8),
                   events=[torch.cuda.Event() for _ in range(V)])
-        nb, lay = blob((("flip", (V,), i32), ("wh", (B, 2), f32), ("meta", (V, B, 8), f32)))
-        Bf["ctl"], Bf["ctl_pin"], Bf["ctl_host"] = torch.zeros(nb, dtype=u8, device=dev), torch.zeros(nb, dtype=u8).pin_memory(), {}
-        for name, shape, dt, o, n in lay:
-            Bf[name] = Bf["ctl"][o:o + n].view(dt).view(shape)
-            Bf["ctl_host"][name] = Bf["ctl_pin"][o:o + n].view(dt).view(shape)
-        nb, lay = blob((("boxes", (B, max_out, 4), f32), ("scores", (B, max_out), f32), ("labels", (B, max_out), i32),
-                        ("src", (B, max_out), i32), ("count", (B,), i32), ("flags", (V, 2), i32)))
-        Bf["stage"], Bf["pin"], Bf["host"] = torch.zeros(nb, dtype=u8, device=dev), torch.zeros(nb, dtype=u8).pin_memory(), {}
-        for name, shape, dt, o, n in lay:
-            Bf["out_" + name if name != "flags" else "flags"] = Bf["stage"][o:o + n].view(dt).view(shape)
-            Bf["host"][name] = Bf["pin"][o:o + n].view(dt).view(shape)
+        Bf["ctl_io"], Bf["out_io"] = Blob(_views_ctl_parts(V, B), dev), Blob(merged_parts(max_out, V, (B,)), dev)
+        Bf.update(Bf["ctl_io"].views, **Bf["out_io"].views, ctl=Bf["ctl_io"].dev, stage=Bf["out_io"].dev)
         self._views = Bf
         return Bf
 

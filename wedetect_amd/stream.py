@@ -25,10 +25,10 @@ Two layers:
                       (pixels + control block = descriptors, tables, letterbox metadata), one tmp arena, two result staging
                       sets, all grown geometrically to the largest batch seen and otherwise never allocated per step.
 
-The in-line path (``predict`` / ``forward``: ``ImageTower.checked_counts``) owns the fp16x3 range guard's logic — recalibrate,
-fp32 fallback, the return to fp16x3.  A streamed step only DETECTS a trip (flags and -1 counts arrive with its results); the
-batch is then run again in line, from the canvas the feed already wrote, and while a tower is in its fp32 fallback every batch
-goes in line, so that the counters and the tower state follow exactly the sequence the serial loop produces.
+The range guard follows the guarded-step protocol of wedetect_amd/guarded.py, with the scheduler in the place of its driver: a
+streamed step only DETECTS a trip (flags and -1 counts arrive with its results); the batch is then run again in line, from the
+canvas the feed already wrote, and while a tower is in its fp32 fallback every batch goes in line, so that the counters and the
+tower state follow exactly the sequence the serial loop produces.
 """
 from __future__ import annotations
 
@@ -369,20 +369,10 @@ class TowerBackend:
         c = s.ctx
         return self.h.tower(c["b"], c["hw"][0], c["hw"][1])
 
-    def _layout(self, tower, res) -> list:
-        """(key, tensor, byte offset) of the packed result blob: the step's result tensors + the two range flags."""
-        out, off = [], 0
-        for k in self.RESULT_KEYS:
-            t = res[k]
-            out.append((k, t, off))
-            off += (t.numel() * t.element_size() + 255) // 256 * 256
-        out.append(("range_flags", tower.step_range_flags, off))
-        off += 256
-        return out, off
-
     @_no_grad
     def issue(self, slot: int) -> None:
         import torch
+        from .guarded import layout, typed_views
         s = self.slots[slot]
         c = s.ctx
         self._feed(s)
@@ -390,7 +380,9 @@ class TowerBackend:
         self.h.calibrate_first(tower, s.canvas)
         text, counts_dev = self.texts(c)
         res = tower.detect(s.canvas, text, c["meta"], text_counts=counts_dev, overlap_post=True, **self.step_kw())
-        layout, total = self._layout(tower, res)
+        # the packed result blob: the step's result tensors + the two range flags
+        src = dict({k: res[k] for k in self.RESULT_KEYS}, range_flags=tower.step_range_flags)
+        total, lay = layout([(k, t.shape, t.dtype) for k, t in src.items()])
         if s.stage is None or s.stage.numel() < total:
             s.stage = torch.empty(total, dtype=torch.uint8, device=self.dev)
             s.pin_out = torch.empty(total, dtype=torch.uint8).pin_memory()
@@ -398,16 +390,15 @@ class TowerBackend:
         s.stage.record_stream(post)
         s.stage.record_stream(self.down_stream)
         with torch.cuda.stream(post):                    # the results are produced there, and overwritten by the next step's post
-            for _, t, off in layout:
-                n = t.numel() * t.element_size()
-                s.stage[off:off + n].view(t.dtype).view(t.shape).copy_(t, non_blocking=True)
+            for k, t in typed_views(s.stage, lay).items():
+                t.copy_(src[k], non_blocking=True)
             s.ev_staged.record(post)
         with torch.cuda.stream(self.down_stream):
             self.down_stream.wait_event(s.ev_staged)
             s.pin_out[:total].copy_(s.stage[:total], non_blocking=True)      # ONE packed D2H per batch
             c["tally"]["d2h"] += 1
             s.ev_d2h.record(self.down_stream)
-        c["layout"], c["tower"] = [(k, t.dtype, tuple(t.shape), off) for k, t, off in layout], tower
+        c["layout"], c["tower"] = lay, tower
         self._tally(c)
 
     def _tally(self, c: dict) -> None:
@@ -421,40 +412,31 @@ class TowerBackend:
 
     @_no_grad
     def collect(self, slot: int):
-        import torch
+        from .guarded import tripped, typed_views
         s = self.slots[slot]
         c = s.ctx
         s.ev_d2h.synchronize()
-        host = {}
-        for k, dt, shape, off in c["layout"]:
-            n = int(np.prod(shape)) * torch.empty((), dtype=dt).element_size()
-            host[k] = s.pin_out[off:off + n].view(dt).view(shape)
+        host = typed_views(s.pin_out, c["layout"])
         tower = c["tower"]
         counts = host["count"].tolist()
-        flags = host["range_flags"].tolist() if tower.precision == "fp16x3" else [0, 0]
-        if min(counts, default=0) < 0 or any(flags):
+        if tripped(counts, [host["range_flags"].tolist()], [tower]):
             return True, []
         return False, [self.result(c, j, host, counts[j], tower) for j in range(c["b"])]
 
     def inline_only(self) -> bool:
-        return any(t.overflowed for t in self.h._towers.values())
+        return self.h.inline_only()
 
     @_no_grad
     def inline(self, slot: int):
-        """The batch through the in-line step and ``checked_counts``, as ``predict`` / ``forward_batch`` run it, from the
-        canvas of this slot (written again: a discarded step may not have reached its feed)."""
+        """The batch through the in-line step (``_TowerHolder.checked_step``), as ``predict`` / ``forward_batch`` run it, from
+        the canvas of this slot (written again: a discarded step may not have reached its feed)."""
         s = self.slots[slot]
         c = s.ctx
         self._feed(s)
         tower = self._tower(s)
         tower.clear_range_flags()                        # a discarded later step may have raised them
         text, counts_dev = self.texts(c)
-        x, h = s.canvas, self.h
-        run = lambda: h.detect(tower, x, text, c["meta"], text_counts=counts_dev, **self.step_kw())
-        res = run()
-        recal = (lambda: h.recalibrate(tower, x)) if h.auto_calibrate else None
-        counts = tower.checked_counts(res, run, recal)
-        h.precision = "fp32" if tower.overflowed else h._asked_precision
+        res, counts = self.h.checked_step(tower, s.canvas, text, c["meta"], text_counts=counts_dev, **self.step_kw())
         host = {}
         for k in self.RESULT_KEYS:
             host[k] = res[k].cpu()
@@ -550,9 +532,7 @@ class MmdetBackend(TowerBackend):
         return c["text"]
 
     def step_kw(self):
-        cfg = self.det.test_cfg
-        return dict(normalize_text=True, score_thr=cfg["score_thr"], iou_thr=cfg["nms"]["iou_threshold"], with_embed=False,
-                    nms="mmcv", nms_param=int(cfg["nms"].get("split_thr", 10000)), **self.det._best_kw())
+        return dict(self.det._step_kw(), **self.det._best_kw())
 
     def result(self, c, j, host, n, tower):
         import torch
