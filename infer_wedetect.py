@@ -13,7 +13,11 @@ bank (``.npy`` / ``.pt``; rows for the K prompts then the blank) instead of runn
 the XLM-R tokenizer files; ``--precision {fp32,fp16x3}``; ``--dump-json`` also writes the kept detections per image;
 ``--tile N`` (default 0 = off) runs every image through ``YOLOWorldDetector.predict_tiled`` — overlapping N x N crops
 (``--tile-overlap``, ``--tile-batch`` tiles per step, ``--edge-margin``) plus one overview of the whole image
-(``--no-overview``), merged on the device — before the same ``--threshold`` / ``--topk`` filter.
+(``--no-overview``), merged on the device — before the same ``--threshold`` / ``--topk`` filter;
+``--exemplar-image PATH --exemplar-boxes "x1,y1,x2,y2:name;..."`` (off by default) builds classes from example boxes of one
+image instead of text (``YOLOWorldDetector.exemplar_bank``; a name that repeats is ONE class with several examples,
+``--anchors-per-box`` anchors are pooled per box, ``--save-bank OUT.pt`` keeps the rows) — with ``--text`` the exemplar classes
+are appended after the text classes, without it they are the whole bank.
 """
 import argparse
 import json
@@ -71,7 +75,27 @@ def parse_args(argv=None):
     parser.add_argument("--prompt-groups", action="store_true",
                         help="score every class as the best of several names: inside --text, '/' separates the names of one class "
                              "(\"person/man/woman,dog/puppy\"); --text-bank then holds one row per NAME plus the blank class")
+    parser.add_argument("--exemplar-image", default=None, help="image that holds the example boxes of --exemplar-boxes")
+    parser.add_argument("--exemplar-boxes", default=None,
+                        help="example boxes in pixels of --exemplar-image, \"x1,y1,x2,y2:name;...\"; a name that repeats is one class "
+                             "with several examples; the classes follow the --text classes")
+    parser.add_argument("--anchors-per-box", default=4, type=int, help="with --exemplar-boxes: anchors pooled per example box, 1..8")
+    parser.add_argument("--save-bank", default=None, help="with --exemplar-boxes: write the [C, 768] exemplar rows to this .pt file")
     args = parser.parse_args(argv)
+    args.exemplars = None
+    if (args.exemplar_image is None) != (args.exemplar_boxes is None):
+        parser.exit(2, "infer_wedetect.py: --exemplar-image and --exemplar-boxes go together\n")
+    if args.exemplar_boxes is not None:
+        try:
+            args.exemplars = parse_exemplar_boxes(args.exemplar_boxes)
+        except ValueError as e:
+            parser.exit(2, f"infer_wedetect.py: --exemplar-boxes: {e}\n")
+        if not 1 <= args.anchors_per_box <= 8:
+            parser.exit(2, "infer_wedetect.py: --anchors-per-box takes 1 .. 8\n")
+        if args.prompt_groups:
+            parser.exit(2, "infer_wedetect.py: --exemplar-boxes is not implemented together with --prompt-groups\n")
+    elif args.save_bank is not None:
+        parser.exit(2, "infer_wedetect.py: --save-bank needs --exemplar-boxes\n")
     if args.prompt_groups and (args.best_class or args.sparse_scores or args.top_names):
         parser.exit(2, "infer_wedetect.py: --prompt-groups excludes --best-class, --sparse-scores and --top-names\n")
     if args.prompt_groups and args.tile > 0:
@@ -89,6 +113,26 @@ def parse_args(argv=None):
     if args.best_class and args.tile > 0:
         parser.exit(2, "infer_wedetect.py: --best-class is not implemented for tiled inference (--tile)\n")
     return args
+
+
+def parse_exemplar_boxes(spec: str):
+    """``"x1,y1,x2,y2:name;..."`` -> (class names in order of first appearance, [(box, class index), ...]); ValueError otherwise."""
+    names, out = [], []
+    for item in [t.strip() for t in spec.split(";") if t.strip()]:
+        coords, sep, name = item.partition(":")
+        vals = [v.strip() for v in coords.split(",")]
+        name = name.strip()
+        if not sep or not name or len(vals) != 4:
+            raise ValueError(f"{item!r} is not x1,y1,x2,y2:name")
+        box = tuple(float(v) for v in vals)
+        if not (box[2] > box[0] and box[3] > box[1]):
+            raise ValueError(f"{item!r}: the box needs a positive width and height")
+        if name not in names:
+            names.append(name)
+        out.append((box, names.index(name)))
+    if not out:
+        raise ValueError("no box given")
+    return names, out
 
 
 def read_texts(spec: str, groups: bool = False):
@@ -169,11 +213,13 @@ def main(argv=None, tokenizer=None):
     model = init_detector(cfg, checkpoint=args.checkpoint, device=args.device, palette=["red"], tokenizer=tokenizer,
                           precision=args.precision)
     test_pipeline = Compose(cfg.test_pipeline)
-    texts = read_texts(args.text, args.prompt_groups)
+    texts = read_texts(args.text, args.prompt_groups) if (args.text or args.exemplars is None) else []
     if not osp.exists(args.output_dir):
         os.makedirs(args.output_dir)
     images = list_images(args.image)
-    if args.text_bank:
+    if not texts:
+        pass                                                 # exemplar classes only
+    elif args.text_bank:
         bank = load_bank(args.text_bank)
         n_rows = sum(len(t) for t in texts) if args.prompt_groups else len(texts)
         if bank.shape != (n_rows, 768):
@@ -182,6 +228,17 @@ def main(argv=None, tokenizer=None):
         model.set_text_embeddings(bank, texts)
     else:
         model.reparameterize(texts)
+    if args.exemplars is not None:
+        ex_names, ex_list = args.exemplars
+        info = test_pipeline(dict(img_id=0, img_path=args.exemplar_image, texts=[[t] for t in ex_names]))
+        ex_bank, ex_info = model.exemplar_bank(info["inputs"].unsqueeze(0), [info["data_samples"]], [ex_list], ex_names,
+                                               anchors_per_box=args.anchors_per_box)
+        print(f"exemplar classes {ex_names}: anchors pooled per class {ex_info['support']}", flush=True)
+        if args.save_bank:
+            torch.save(ex_bank.cpu(), args.save_bank)
+        bank = torch.cat([model.text_feats.to(ex_bank.device), ex_bank]) if texts else ex_bank
+        texts = texts + [[t] for t in ex_names]              # appended after the text classes (their blank class included)
+        model.set_text_embeddings(bank, texts)
     results = []
     for n, image_path in enumerate(images):
         if args.tile > 0:

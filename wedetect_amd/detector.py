@@ -19,6 +19,7 @@ device / the built library raises.
 """
 from __future__ import annotations
 
+import math
 import os
 from collections import OrderedDict
 from typing import Callable, Dict, List, Optional, Sequence, Tuple, Union
@@ -240,7 +241,11 @@ class _TowerHolder:
         """The in-line step: ``detect``, then the step's counts through ``ImageTower.checked_counts`` — one D2H sync per
         batch and the fp16x3 range guard, which may recalibrate, repeat the step or fall back to fp32 — then the holder's
         precision follows the tower.  Returns (the tower's result buffers, counts list)."""
-        run = lambda: self.detect(tower, images_u8, text, meta, text_counts=text_counts, **kw)
+        return self.checked_run(tower, images_u8, lambda: self.detect(tower, images_u8, text, meta, text_counts=text_counts, **kw))
+
+    def checked_run(self, tower, images_u8, run):
+        """``run()`` (a closure that issues one tower step on ``images_u8`` and returns a result with ``count``) under the range
+        guard of ``checked_step``: the guard may recalibrate, repeat ``run`` or fall back to fp32."""
         res = run()
         recal = (lambda: self.recalibrate(tower, images_u8)) if self.auto_calibrate else None
         counts = tower.checked_counts(res, run, recal)
@@ -655,6 +660,47 @@ def pack_image_banks(banks: Sequence[torch.Tensor], device=None) -> Tuple[torch.
     return packed, torch.tensor(ks, dtype=torch.int32).to(packed.device)
 
 
+def plan_exemplars(exemplars, names=None, anchors_per_box: int = 4, min_iou: float = 0.1) -> dict:
+    """The host side of an exemplar-bank build (include/wedetect_hip_exemplar.h): ``exemplars[b]`` = the list of
+    ``(box_xyxy_in_original_pixels, class_index)`` of image b -> ``ex_boxes`` fp32 [B, max_ex, 4], ``ex_count`` int32 [B], the
+    classes' slot lists ``cls_off`` int32 [C + 1] / ``cls_slot`` int32 [T] (class by class: images in batch order, an image's
+    examples in list order, an example's anchors by rank), ``cls_examples`` (the (b, e) pairs of every class) and ``names``.
+    ValueError for a box with non-positive width or height (or a non-finite coordinate), a class index outside 0 .. C - 1, a
+    class without an example, more than 64 examples in one image; C = len(names), or the largest index + 1 without names."""
+    from . import exemplar as EX
+    m, min_iou = EX.check_m(anchors_per_box), EX.check_min_iou(min_iou)
+    flat = [(b, e, box, cls) for b, lst in enumerate(exemplars) for e, (box, cls) in enumerate(lst)]
+    if not flat:
+        raise ValueError("exemplars: no example box in the batch")
+    for b, e, box, cls in flat:
+        box = [float(v) for v in box]
+        if len(box) != 4 or not all(math.isfinite(v) for v in box) or not (box[2] > box[0] and box[3] > box[1]):
+            raise ValueError(f"exemplars[{b}][{e}]: box {box} must be (x1, y1, x2, y2) with positive width and height")
+        if isinstance(cls, bool) or int(cls) != cls or cls < 0:
+            raise ValueError(f"exemplars[{b}][{e}]: class index {cls!r} must be a non-negative int")
+    n_cls = len(names) if names is not None else max(int(cls) for *_, cls in flat) + 1
+    names = [str(n) for n in names] if names is not None else [f"exemplar_{c}" for c in range(n_cls)]
+    max_ex = max(len(lst) for lst in exemplars)
+    if max_ex > EX.MAX_EX:
+        raise ValueError(f"exemplars: at most {EX.MAX_EX} example boxes per image, got {max_ex}")
+    ex_boxes, ex_count = np.zeros((len(exemplars), max_ex, 4), np.float32), np.zeros(len(exemplars), np.int32)
+    cls_examples: List[List[Tuple[int, int]]] = [[] for _ in range(n_cls)]
+    for b, e, box, cls in flat:
+        if int(cls) >= n_cls:
+            raise ValueError(f"exemplars[{b}][{e}]: class index {cls} outside the {n_cls} names")
+        ex_boxes[b, e] = box
+        ex_count[b] = max(ex_count[b], e + 1)
+        cls_examples[int(cls)].append((b, e))
+    for c, lst in enumerate(cls_examples):
+        if not lst:
+            raise ValueError(f"class {c} ({names[c]!r}) has no example box")
+    s = max_ex * m
+    slots = [[b * s + e * m + j for b, e in lst for j in range(m)] for lst in cls_examples]
+    cls_off = np.cumsum([0] + [len(v) for v in slots]).astype(np.int32)
+    return dict(ex_boxes=ex_boxes, ex_count=ex_count, cls_off=cls_off, cls_slot=np.concatenate(slots).astype(np.int32),
+                cls_examples=cls_examples, names=names, m=m, min_iou=min_iou, max_ex=max_ex)
+
+
 class MultiModalYOLOBackbone:
     """``model.backbone`` of the reference detector (mm_backbone.py:594-656) as far as inference callers touch it:
     ``forward_text(texts)`` and ``with_text_model``.  The image side is the fused ``ImageTower``; it has no
@@ -957,6 +1003,78 @@ class YOLOWorldDetector(_DeviceModule):
             s.pred_instances = inst
             out.append(s)
         return out
+
+    # -- exemplar prompts --------------------------------------------------------------------
+    @torch.no_grad()
+    def exemplar_bank(self, batch_inputs, batch_data_samples, exemplars, names=None, *, anchors_per_box: int = 4,
+                      min_iou: float = 0.1):
+        """Class-bank rows from example boxes instead of text ("find more things like the one in this box").  ``batch_inputs`` /
+        ``batch_data_samples`` as in ``predict``; ``exemplars[b]``: the list of ``(box_xyxy_in_original_pixels, class_index)`` of
+        image b — the geometry comes from the samples' ``scale_factor`` / ``pad_param`` as in ``predict``.  Every example box takes
+        the ``anchors_per_box`` anchors whose decoded boxes overlap it best (IoU > ``min_iou``); a class's row is the IoU-weighted
+        mean of their L2-normalised region embeddings, L2-normalised (include/wedetect_hip_exemplar.h).
+
+        Returns ``(bank, info)``: ``bank`` fp32 [C, 768] on the device, unit rows, C = len(names) or the largest class index + 1;
+        ``info``: ``names``, ``support`` (anchors pooled per class), ``anchors`` / ``ious`` ([B, max_ex, anchors_per_box] host
+        tensors, -1 / 0 in empty slots) and ``examples`` (the (image, example) pairs of every class).
+
+        The rows are used exactly like text rows: ``set_text_embeddings(bank)``, per-image banks, or mixed —
+        ``torch.cat([text_bank, exemplar_bank])`` is a valid bank, because text rows are L2-normalised on the device and these
+        prototypes are unit rows already.
+
+        ValueError: a box with non-positive width or height, a class index with no example, a class no anchor was assigned to
+        (support 0; the message names the class and the best IoU any of its boxes reaches).  The bank is never non-finite: the
+        build runs under the range guard of ``predict`` (a trip in fp16x3 repeats it, at last on the fp32 kernels) and a result
+        that is non-finite even then raises RuntimeError."""
+        plan = plan_exemplars(exemplars, names, anchors_per_box, min_iou)
+        dev = self._h.device
+        if dev is None:
+            raise RuntimeError("model is not on a HIP device: call .cuda()")
+        xs = [x for x in batch_inputs]
+        samples = list(batch_data_samples) if batch_data_samples is not None else [None] * len(xs)
+        if len(samples) != len(xs) or len(exemplars) != len(xs):
+            raise ValueError(f"{len(xs)} inputs but {len(samples)} data samples and {len(exemplars)} exemplar lists")
+        hh, ww = _batch_hw(xs)
+        x = _nhwc_u8(xs, dev)
+        tower = self._h.tower(len(xs), hh, ww)
+        meta = torch.tensor([letterbox_meta(_meta_of(s), hh, ww, True) for s in samples], dtype=torch.float32, device=dev)
+        d = {k: torch.from_numpy(plan[k]).to(dev) for k in ("ex_boxes", "ex_count", "cls_off", "cls_slot")}
+        m = plan["m"]
+        self._h.calibrate_first(tower, x)
+        run = lambda: tower.exemplar_bank(x, meta, d["ex_boxes"], d["ex_count"], d["cls_off"], d["cls_slot"], m, plan["min_iou"])
+        res, counts = self._h.checked_run(tower, x, run)
+        support = counts[:-1]
+        anchors = res["sel_anchors"].view(len(xs), plan["max_ex"], m).cpu()
+        ious = res["sel_iou"].view(len(xs), plan["max_ex"], m).cpu()
+        for c, n in enumerate(support):
+            if n == 0:
+                best = self._best_iou(tower, d, meta, plan["cls_examples"][c], plan["max_ex"])
+                raise ValueError(f"exemplar class {c} ({plan['names'][c]!r}): no anchor overlaps its example boxes with IoU > "
+                                 f"{plan['min_iou']:g} (best IoU {best:.4f}); lower min_iou or check the boxes")
+        bank = res["bank"].clone()
+        if not bool(torch.isfinite(bank).all()):
+            raise RuntimeError("exemplar bank is non-finite after the range guard")
+        return bank, dict(names=plan["names"], support=support, anchors=anchors, ious=ious, examples=plan["cls_examples"])
+
+    @staticmethod
+    def _best_iou(tower, d: dict, meta: torch.Tensor, examples, max_ex: int) -> float:
+        """The largest IoU any anchor reaches with the given (image, example) boxes: the assignment with one anchor and no
+        threshold, on the boxes the tower's last head decoded (the error path of ``exemplar_bank`` only)."""
+        from . import exemplar as EX
+        a = torch.empty(tower.B, max_ex, dtype=torch.int32, device=tower.dev)
+        iou, cnt = torch.empty(tower.B, max_ex, dtype=torch.float32, device=tower.dev), torch.empty(tower.B, dtype=torch.int32, device=tower.dev)
+        EX.exemplar_assign(tower.boxes, tower.ntot, d["ex_boxes"], d["ex_count"], meta, max_ex, tower.B, 1, 0.0, a, iou, cnt)
+        iou = iou.cpu()
+        return max(float(iou[b, e]) for b, e in examples)
+
+    def set_exemplar_bank(self, batch_inputs, batch_data_samples, exemplars, names=None, *, anchors_per_box: int = 4,
+                          min_iou: float = 0.1):
+        """``exemplar_bank(...)`` followed by ``set_text_embeddings(bank, [[n] for n in names])``: the detector then predicts the
+        exemplar classes (names default to ``exemplar_<index>``).  Returns ``(bank, info)``."""
+        bank, info = self.exemplar_bank(batch_inputs, batch_data_samples, exemplars, names, anchors_per_box=anchors_per_box,
+                                        min_iou=min_iou)
+        self.set_text_embeddings(bank, [[n] for n in info["names"]])
+        return bank, info
 
     def predict_stream(self, data_infos: Sequence[dict], batch_size: int, pipeline_cfg, *, rescale: bool = True,
                        decode_workers: Optional[int] = None, stats: Optional[dict] = None):

@@ -303,6 +303,7 @@ class ImageTower:
         self._kept_s: Optional[torch.Tensor] = None           # [3, B * max_out, K] the unfolded similarity GEMM on the kept rows' embeddings
         self._kept_perm: Optional[torch.Tensor] = None        # [B, max_out] int32: where wd_kept_rows_reorder took each kept row from
         self._scores_fold: Optional[tuple] = None             # (fold entry, sigmoid) when ``scores`` holds a folded similarity
+        self._ex: Optional[dict] = None                       # exemplar_bank(): buffers sized by (B, max_ex, m) and by the class count, kept between calls
         self.overflowed = False
         self.fp16x3_trips = 0            # range-guard trips of this tower (each: one re-calibration attempt, then the fp32 fallback)
         self.fp16x3_retries = 0          # returns from the fp32 fallback to the fp16x3 kernels
@@ -1516,8 +1517,62 @@ class ImageTower:
             FD.kept_rows_select(self._kept_t, EMBED_DIM, self.off[1], self.off[2], self.out_anchors, self.out_count, self.max_out,
                                 self.B, self.out_embed, self._kept_perm)
 
+    # ------------------------------------------------------------------ exemplar prompts
+    def exemplar_bank(self, images_u8: torch.Tensor, meta: torch.Tensor, ex_boxes: torch.Tensor, ex_count: torch.Tensor,
+                      cls_off: torch.Tensor, cls_slot: torch.Tensor, m: int = 4, min_iou: float = 0.1) -> Dict[str, torch.Tensor]:
+        """Class-bank rows from example boxes (include/wedetect_hip_exemplar.h): ``ex_boxes`` fp32 [B, max_ex, 4] in
+        original-image pixels with ``ex_count`` int32 [B] of them per image, ``meta`` [B, 8] as in postprocess(); ``cls_off`` int32
+        [C + 1] / ``cls_slot`` int32 [T] list every class's example slots ``b * max_ex * m + e * m + j``.  All device tensors.
+
+        features() (the head stops at c2, as in a folded step) -> wd_exemplar_assign (the ``m`` anchors that overlap each example
+        best) -> the kept-rows route of _kept_rows with max_out replaced by S = max_ex * m: wd_kept_rows_gather, then each level's
+        embedding GEMM, the instantiation the embedding conv runs on with its ``a_key`` scales, so the rows are ``embed[b, anchor]``
+        bit for bit and [B, N, 768] is never written -> wd_exemplar_pool.  In line on the current stream.  The c2 lifetime rule of
+        _kept_rows holds here too: features() starts with wait_post(), and the head of every later step is issued behind this
+        stream's work.
+
+        Returns ``bank`` fp32 [C, 768] (unit rows; an all-zero row where ``support`` is 0), ``support`` int32 [C], ``sel_anchors``
+        int32 / ``sel_iou`` fp32 [B, S], ``sel_count`` int32 [B] and ``count`` int32 [C + 1] for ``checked_counts()``: the supports,
+        then -1 where a supported class pooled to a non-finite row (0 otherwise).  The tensors are the tower's buffers, rewritten by
+        the next call."""
+        from . import exemplar as EX
+        m, min_iou = EX.check_m(m), EX.check_min_iou(min_iou)
+        if ex_boxes.dim() != 3 or ex_boxes.shape[0] != self.B or ex_boxes.shape[2] != 4 or not 1 <= ex_boxes.shape[1] <= EX.MAX_EX:
+            raise ValueError(f"ex_boxes must be [{self.B}, 1..{EX.MAX_EX}, 4], got {tuple(ex_boxes.shape)}")
+        max_ex, C = int(ex_boxes.shape[1]), int(cls_off.numel()) - 1
+        if C < 1:
+            raise ValueError("cls_off must hold C + 1 >= 2 offsets")
+        S, rows = max_ex * m, self.B * max_ex * m
+        ex = self._ex
+        if ex is None or ex["key"] != (max_ex, m):
+            i32 = dict(dtype=torch.int32, device=self.dev)
+            ex = self._ex = dict(key=(max_ex, m), g=torch.empty(3, rows, CLS_MID, dtype=torch.float32, device=self.dev),
+                                 t=torch.empty(3, rows, EMBED_DIM, dtype=torch.float32, device=self.dev),
+                                 sel_anchors=torch.empty(self.B, S, **i32), sel_count=torch.empty(self.B, **i32),
+                                 sel_iou=torch.empty(self.B, S, dtype=torch.float32, device=self.dev), bank=None, support=None)
+        if ex["bank"] is None or ex["bank"].shape[0] != C:
+            ex["bank"] = torch.empty(C, EMBED_DIM, dtype=torch.float32, device=self.dev)
+            ex["support"] = torch.empty(C, dtype=torch.int32, device=self.dev)
+        fold = {"exemplar": True}                 # no folded bank: only tells the head to stop at c2 (``embed`` materialises on demand)
+        self.features(images_u8, None, _fold=fold)
+        self._mark_c2(fold)
+        EX.exemplar_assign(self.boxes, self.ntot, ex_boxes, ex_count, meta, max_ex, self.B, m, min_iou, ex["sel_anchors"],
+                           ex["sel_iou"], ex["sel_count"])
+        FD.kept_rows_gather([c[1] for c in self.hc], self.nl, CLS_MID, ex["sel_anchors"], ex["sel_count"], S, self.B, ex["g"])
+        flags = L.SPLIT_A if self._neck_split() else 0
+        for l in range(3):
+            self._conv(ex["g"][l], f"head{l}.embed.w", f"head{l}.embed.b", ex["t"][l], hin=1, win=S, cin=CLS_MID, lda=CLS_MID,
+                       n=EMBED_DIM, ldc=EMBED_DIM, c_batch_stride=S, split_flags=flags, a_key=f"h{l}.c2")
+        EX.exemplar_pool(ex["t"], EMBED_DIM, self.off[1], self.off[2], ex["sel_anchors"], ex["sel_iou"], rows, cls_off, cls_slot, C,
+                         ex["bank"], ex["support"])
+        bank, support = ex["bank"], ex["support"]
+        bad = ((support > 0) & (bank.abs().amax(dim=1) == 0)).any() | ~torch.isfinite(bank).all()
+        count = torch.cat([support, -bad.to(torch.int32).view(1)])
+        return dict(bank=bank, support=support, sel_anchors=ex["sel_anchors"], sel_iou=ex["sel_iou"], sel_count=ex["sel_count"],
+                    count=count)
+
     # ------------------------------------------------------------------ post-process
-    NMS_MODES = {"vanilla": L.NMS_VANILLA, "torchvision": L.NMS_TORCHVISION, "mmcv": L.NMS_MMCV}
+    NMS_MODES ={"vanilla": L.NMS_VANILLA, "torchvision": L.NMS_TORCHVISION, "mmcv": L.NMS_MMCV}
 
     def _nms_args(self, nms: str, nms_param: Optional[int], nms_device: str, iou_thr: float, agnostic: bool = False):
         """(nms_mode, mode_param, iou threshold) of wd_nms_gather / wd_nms_gather_labeled for the keywords of the postprocess methods."""
