@@ -17,7 +17,10 @@ the XLM-R tokenizer files; ``--precision {fp32,fp16x3}``; ``--dump-json`` also w
 ``--exemplar-image PATH --exemplar-boxes "x1,y1,x2,y2:name;..."`` (off by default) builds classes from example boxes of one
 image instead of text (``YOLOWorldDetector.exemplar_bank``; a name that repeats is ONE class with several examples,
 ``--anchors-per-box`` anchors are pooled per box, ``--save-bank OUT.pt`` keeps the rows) — with ``--text`` the exemplar classes
-are appended after the text classes, without it they are the whole bank.
+are appended after the text classes, without it they are the whole bank; ``--tune-steps N`` (default 0 = off; ``--tune-lr``)
+then refines the exemplar rows on the same boxes by N Adam steps with both towers frozen
+(``YOLOWorldDetector.tune_bank``) before detection: with ``--text`` the text rows are frozen and serve as negatives, and
+``--save-bank`` keeps the tuned rows.
 """
 import argparse
 import json
@@ -81,8 +84,16 @@ def parse_args(argv=None):
                              "with several examples; the classes follow the --text classes")
     parser.add_argument("--anchors-per-box", default=4, type=int, help="with --exemplar-boxes: anchors pooled per example box, 1..8")
     parser.add_argument("--save-bank", default=None, help="with --exemplar-boxes: write the [C, 768] exemplar rows to this .pt file")
+    parser.add_argument("--tune-steps", default=0, type=int,
+                        help="with --exemplar-boxes: refine the exemplar rows on the same boxes by this many Adam steps, towers "
+                             "frozen (--text rows are frozen negatives); 0 = off")
+    parser.add_argument("--tune-lr", default=1e-2, type=float, help="with --tune-steps: Adam's learning rate (a parameter, not a tuned value)")
     args = parser.parse_args(argv)
     args.exemplars = None
+    if args.tune_steps < 0 or not 0 < args.tune_lr < float("inf"):
+        parser.exit(2, "infer_wedetect.py: --tune-steps takes a count >= 0 and --tune-lr a positive rate\n")
+    if args.tune_steps and args.exemplar_boxes is None:
+        parser.exit(2, "infer_wedetect.py: --tune-steps needs --exemplar-boxes\n")
     if (args.exemplar_image is None) != (args.exemplar_boxes is None):
         parser.exit(2, "infer_wedetect.py: --exemplar-image and --exemplar-boxes go together\n")
     if args.exemplar_boxes is not None:
@@ -234,9 +245,18 @@ def main(argv=None, tokenizer=None):
         ex_bank, ex_info = model.exemplar_bank(info["inputs"].unsqueeze(0), [info["data_samples"]], [ex_list], ex_names,
                                                anchors_per_box=args.anchors_per_box)
         print(f"exemplar classes {ex_names}: anchors pooled per class {ex_info['support']}", flush=True)
+        bank = torch.cat([model.text_feats.to(ex_bank.device), ex_bank]) if texts else ex_bank
+        if args.tune_steps:
+            # the exemplar rows learn on the same boxes; the text rows (their blank class included) are frozen negatives
+            n_text = bank.shape[0] - ex_bank.shape[0]
+            bank, tn = model.tune_bank(info["inputs"].unsqueeze(0), [info["data_samples"]], [[(box, n_text + c) for box, c in ex_list]],
+                                       init=bank, steps=args.tune_steps, lr=args.tune_lr, frozen_rows=list(range(n_text)),
+                                       anchors_per_box=args.anchors_per_box)
+            ex_bank = bank[n_text:]
+            print(f"tuned {len(ex_names)} exemplar rows beside {n_text} frozen rows: loss {tn['loss'][0]:.4f} -> {tn['loss'][-1]:.4f} "
+                  f"before the last of {args.tune_steps} steps, positives per class {tn['positives'][n_text:]}", flush=True)
         if args.save_bank:
             torch.save(ex_bank.cpu(), args.save_bank)
-        bank = torch.cat([model.text_feats.to(ex_bank.device), ex_bank]) if texts else ex_bank
         texts = texts + [[t] for t in ex_names]              # appended after the text classes (their blank class included)
         model.set_text_embeddings(bank, texts)
     results = []

@@ -701,6 +701,34 @@ def plan_exemplars(exemplars, names=None, anchors_per_box: int = 4, min_iou: flo
                 cls_examples=cls_examples, names=names, m=m, min_iou=min_iou, max_ex=max_ex)
 
 
+def plan_tune_boxes(boxes, n_rows=None, anchors_per_box: int = 4, min_iou: float = 0.1) -> dict:
+    """The host side of a bank-tuning batch (include/wedetect_hip_tune.h): ``boxes[b]`` = the list of
+    ``(box_xyxy_in_original_pixels, class_index)`` of image b -> ``ex_boxes`` fp32 [B, max_ex, 4], ``ex_count`` int32 [B],
+    ``gt_cls`` int32 [B, max_ex].  The box checks of ``plan_exemplars``; unlike there a class may be without a box (frozen rows,
+    classes that learn from negatives only) and an image may be without one (all its anchors are negatives).  ``n_rows``: the rows
+    of the bank the class indices refer to, when known."""
+    from . import exemplar as EX
+    m, min_iou = EX.check_m(anchors_per_box), EX.check_min_iou(min_iou)
+    flat = [(b, e, box, cls) for b, lst in enumerate(boxes) for e, (box, cls) in enumerate(lst)]
+    for b, e, box, cls in flat:
+        box = [float(v) for v in box]
+        if len(box) != 4 or not all(math.isfinite(v) for v in box) or not (box[2] > box[0] and box[3] > box[1]):
+            raise ValueError(f"boxes[{b}][{e}]: box {box} must be (x1, y1, x2, y2) with positive width and height")
+        if isinstance(cls, bool) or int(cls) != cls or cls < 0:
+            raise ValueError(f"boxes[{b}][{e}]: class index {cls!r} must be a non-negative int")
+        if n_rows is not None and int(cls) >= n_rows:
+            raise ValueError(f"boxes[{b}][{e}]: class index {cls} outside the {n_rows} rows of the bank")
+    max_ex = max([len(lst) for lst in boxes] + [1])
+    if max_ex > EX.MAX_EX:
+        raise ValueError(f"boxes: at most {EX.MAX_EX} labelled boxes per image, got {max_ex}")
+    ex_boxes, ex_count = np.zeros((len(boxes), max_ex, 4), np.float32), np.zeros(len(boxes), np.int32)
+    gt_cls = np.zeros((len(boxes), max_ex), np.int32)
+    for b, e, box, cls in flat:
+        ex_boxes[b, e], gt_cls[b, e] = box, int(cls)
+        ex_count[b] = max(ex_count[b], e + 1)
+    return dict(ex_boxes=ex_boxes, ex_count=ex_count, gt_cls=gt_cls, m=m, min_iou=min_iou, max_ex=max_ex)
+
+
 class MultiModalYOLOBackbone:
     """``model.backbone`` of the reference detector (mm_backbone.py:594-656) as far as inference callers touch it:
     ``forward_text(texts)`` and ``with_text_model``.  The image side is the fused ``ImageTower``; it has no
@@ -743,6 +771,7 @@ class YOLOWorldDetector(_DeviceModule):
         # prompt groups (also ``model.prompt_groups`` of a config): every class is scored as the best of ALL its prompts — the
         # synonym lists of the class-text files — instead of its first caption (wedetect_amd/groups.py, engine.ImageTower.detect)
         self.prompt_groups = bool(prompt_groups)
+        self._tuner = None                                   # tune_bank's cache between fit=False calls (tune.BankTuner)
         if self.prompt_groups and (best_class or sparse_scores or top_names):
             raise ValueError("prompt_groups=True is a multi-label dense step of its own: it excludes best_class, sparse_scores and top_names")
         self._plans: Dict[Tuple[str, ...], object] = {}      # first captions -> groups.PromptGroups of that bank (prompt_groups only)
@@ -1073,6 +1102,122 @@ class YOLOWorldDetector(_DeviceModule):
         exemplar classes (names default to ``exemplar_<index>``).  Returns ``(bank, info)``."""
         bank, info = self.exemplar_bank(batch_inputs, batch_data_samples, exemplars, names, anchors_per_box=anchors_per_box,
                                         min_iou=min_iou)
+        self.set_text_embeddings(bank, [[n] for n in info["names"]])
+        return bank, info
+
+    # -- bank tuning --------------------------------------------------------------------
+    def tune_bank(self, batch_inputs, batch_data_samples, boxes, names=None, *, init="exemplar", steps: int = 50, lr: float = 1e-2,
+                  betas=(0.9, 0.999), eps: float = 1e-8, frozen_rows=None, anchors_per_box: int = 4, min_iou: float = 0.1,
+                  fit: bool = True, max_cache_bytes: int = 8 << 30):
+        """Learn class-bank rows from labelled boxes with both towers frozen (include/wedetect_hip_tune.h).  ``batch_inputs`` /
+        ``batch_data_samples`` as in ``predict``; ``boxes[b]``: the list of ``(box_xyxy_in_original_pixels, class_index)`` of image
+        b, the geometry coming from the samples exactly as in ``exemplar_bank``.  The batch's region embeddings and its static
+        targets (every box's ``anchors_per_box`` best-overlapping anchors, IoU > ``min_iou``, target = IoU) are cached on the device;
+        with ``fit=False`` the call only adds the batch and returns None, so more images than one batch are added by calling it
+        repeatedly, and the last call (``fit=True``) runs ``steps`` Adam steps over everything cached and empties the cache.
+        ``init`` is used by the fitting call alone (a ``fit=False`` call checks it and computes nothing from it); a call that raises
+        leaves the batches added before it in the cache, and ``tune_reset()`` empties the cache.
+
+        ``init``: a [K, 768] bank; ``"text"``, the current text bank; ``"exemplar"``, the pooled prototypes of THE FITTING call's
+        boxes (``exemplar_bank``: every class needs a box in that batch, so tuning over several batches wants an explicit bank).
+        Class indices are rows of that bank.  ``frozen_rows`` (indices or a bool mask of K) marks rows that serve as negatives only
+        — new classes learned beside a text bank: they come back as the normalised start rows, bit for bit (every row of ``init`` is
+        L2-normalised once before the first step; normalising a unit row can move an ulp).  ``steps`` and ``lr`` are parameters,
+        not tuned values.  A class without a positive anchor is allowed (it learns from negatives only; ``info["no_positive"]``).
+
+        Returns ``(bank, info)``: unit rows fp32 [K, 768], used like any bank (``set_text_embeddings``, per-image banks, every
+        detection mode); ``info``: ``names``, ``loss`` (before each step), ``positives`` per class, ``no_positive``, ``plan``,
+        ``status``, ``init``.  Detection quality after tuning is unmeasured: no trained weights have been run through this."""
+        from . import tune as TN
+        if self.prompt_groups:
+            raise NotImplementedError("tune_bank with prompt_groups=True is not implemented (it learns one row per class)")
+        if isinstance(init, torch.Tensor):
+            TN.check_bank(init, "init")
+        elif init not in ("text", "exemplar"):
+            raise ValueError(f"init: a [K, {EMBED_DIM}] bank, \"text\" or \"exemplar\" is supported, got {init!r}")
+        if init == "text":
+            if self.text_feats is None:
+                raise ValueError("init=\"text\": no text bank is set (reparameterize / set_text_embeddings)")
+            TN.check_bank(self.text_feats, "init=\"text\": the current text bank")
+        n_rows = None if init == "exemplar" else int((init if isinstance(init, torch.Tensor) else self.text_feats).shape[0])
+        if names is not None and n_rows is not None and len(names) != n_rows:
+            raise ValueError(f"{len(names)} names for a bank of {n_rows} rows")
+        plan = plan_tune_boxes(boxes, n_rows, anchors_per_box, min_iou)
+        dev = self._h.device
+        if dev is None:
+            raise RuntimeError("model is not on a HIP device: call .cuda()")
+        xs = [x for x in batch_inputs]
+        samples = list(batch_data_samples) if batch_data_samples is not None else [None] * len(xs)
+        if len(samples) != len(xs) or len(boxes) != len(xs):
+            raise ValueError(f"{len(xs)} inputs but {len(samples)} data samples and {len(boxes)} box lists")
+        bank0 = None
+        if not fit:
+            pass                                             # only the fitting call's init is used: nothing to compute here
+        elif init == "exemplar":
+            bank0, _ = self.exemplar_bank(batch_inputs, batch_data_samples, boxes, names, anchors_per_box=anchors_per_box, min_iou=min_iou)
+        elif init == "text":
+            bank0 = self.text_feats
+        else:
+            bank0 = init.to(dev)
+        hh, ww = _batch_hw(xs)
+        x = _nhwc_u8(xs, dev)
+        tower = self._h.tower(len(xs), hh, ww)
+        meta = torch.tensor([letterbox_meta(_meta_of(s), hh, ww, True) for s in samples], dtype=torch.float32, device=dev)
+        d = {k: torch.from_numpy(plan[k]).to(dev) for k in ("ex_boxes", "ex_count", "gt_cls")}
+        tuner = self._tuner
+        if tuner is None:
+            tuner = self._tuner = TN.BankTuner(tower, max_cache_bytes)
+        tuner.max_cache_bytes = int(max_cache_bytes)
+        self._h.calibrate_first(tower, x)
+        first = len(tuner.chunks)
+
+        def run():
+            tuner.truncate(first)                            # a repeat under the range guard replaces the chunk
+            c = tuner.add_batch(x, meta, d["ex_boxes"], d["ex_count"], d["gt_cls"], plan["m"], plan["min_iou"], tower=tower)
+            bad = ~torch.isfinite(c["E"]).all()
+            return dict(count=torch.cat([c["sel_count"], -bad.to(torch.int32).view(1)]))
+        try:
+            with torch.no_grad():
+                self._h.checked_run(tower, x, run)
+        except BaseException:
+            tuner.truncate(first)                            # the cache holds whole batches only
+            raise
+        if not fit:
+            return None
+        K = int(bank0.shape[0])
+        trainable = torch.ones(K, dtype=torch.bool)
+        if frozen_rows is not None:
+            fr = torch.as_tensor(frozen_rows)
+            if fr.dtype == torch.bool:
+                if tuple(fr.shape) != (K,):
+                    raise ValueError(f"frozen_rows: a bool mask of {K} rows is supported, got {tuple(fr.shape)}")
+                trainable = ~fr.cpu()
+            else:
+                if fr.numel() and (int(fr.min()) < 0 or int(fr.max()) >= K):
+                    raise ValueError(f"frozen_rows: indices in 0 .. {K - 1} are supported")
+                trainable[fr.to(torch.int64).cpu()] = False
+        try:
+            with torch.no_grad():
+                bank, info = tuner.fit(bank0, steps, lr=lr, betas=betas, eps=eps, trainable=trainable)
+        finally:
+            self._tuner = None                               # the cache is spent either way
+        if not bool(torch.isfinite(bank).all()):
+            raise RuntimeError("tuned bank is non-finite")
+        info["names"] = [str(n) for n in names] if names is not None else [f"{'exemplar' if init == 'exemplar' else 'class'}_{c}" for c in range(K)]
+        for k in ("w", "m", "v"):
+            info.pop(k)
+        info["init"] = bank0.detach().clone()                # the rows the steps started from, before normalisation
+        return bank, info
+
+    def tune_reset(self) -> None:
+        """Drop the batches ``tune_bank(..., fit=False)`` has cached."""
+        self._tuner = None
+
+    def set_tuned_bank(self, batch_inputs, batch_data_samples, boxes, names=None, **kw):
+        """``tune_bank(...)`` followed by ``set_text_embeddings(bank, [[n] for n in names])``.  Returns ``(bank, info)``."""
+        if kw.get("fit", True) is False:
+            raise ValueError("set_tuned_bank fits: add earlier batches with tune_bank(..., fit=False)")
+        bank, info = self.tune_bank(batch_inputs, batch_data_samples, boxes, names, **kw)
         self.set_text_embeddings(bank, [[n] for n in info["names"]])
         return bank, info
 
