@@ -88,8 +88,32 @@ def parse_args(argv=None):
                         help="with --exemplar-boxes: refine the exemplar rows on the same boxes by this many Adam steps, towers "
                              "frozen (--text rows are frozen negatives); 0 = off")
     parser.add_argument("--tune-lr", default=1e-2, type=float, help="with --tune-steps: Adam's learning rate (a parameter, not a tuned value)")
+    parser.add_argument("--track", action="store_true",
+                        help="treat the images of an --image directory as ONE video in name order: detections keep their ids from "
+                             "frame to frame (associated on the device from boxes and region embeddings); --dump-json gains "
+                             "\"track_id\" per detection (0 = no track)")
+    parser.add_argument("--track-batch", default=8, type=int, help="with --track: consecutive frames per tower step")
+    parser.add_argument("--track-high", default=0.5, type=float, help="with --track: first round takes scores >= this")
+    parser.add_argument("--track-low", default=0.1, type=float, help="with --track: second round takes scores from this up to --track-high")
+    parser.add_argument("--track-new", default=0.6, type=float, help="with --track: an unmatched detection starts a track from this score")
+    parser.add_argument("--track-match", default=0.3, type=float, help="with --track: least similarity of a first-round match")
+    parser.add_argument("--track-iou2", default=0.5, type=float, help="with --track: least IoU of a second-round match")
+    parser.add_argument("--track-w-iou", default=0.5, type=float, help="with --track: weight of the IoU against the appearance term, 0 .. 1")
+    parser.add_argument("--track-max-age", default=30, type=int, help="with --track: frames a track survives unmatched")
+    parser.add_argument("--track-labels", action="store_true", help="with --track: a match needs equal labels")
     args = parser.parse_args(argv)
     args.exemplars = None
+    if not args.track and any(a.startswith("--track-") for a in (sys.argv[1:] if argv is None else argv)):
+        parser.exit(2, "infer_wedetect.py: a --track-... option needs --track\n")
+    if args.track:
+        if args.track_batch < 1:
+            parser.exit(2, "infer_wedetect.py: --track-batch takes a count >= 1\n")
+        if args.prompt_groups or args.tile > 0:
+            parser.exit(2, "infer_wedetect.py: --track is not implemented together with --prompt-groups or --tile\n")
+        try:
+            track_params(args)
+        except ValueError as e:
+            parser.exit(2, f"infer_wedetect.py: --track: {e}\n")
     if args.tune_steps < 0 or not 0 < args.tune_lr < float("inf"):
         parser.exit(2, "infer_wedetect.py: --tune-steps takes a count >= 0 and --tune-lr a positive rate\n")
     if args.tune_steps and args.exemplar_boxes is None:
@@ -124,6 +148,28 @@ def parse_args(argv=None):
     if args.best_class and args.tile > 0:
         parser.exit(2, "infer_wedetect.py: --best-class is not implemented for tiled inference (--tile)\n")
     return args
+
+
+def track_params(args):
+    """The --track-... flags as a ``track.TrackParams`` (ValueError when they contradict each other)."""
+    from wedetect_amd.track import TrackParams
+    return TrackParams(high_thr=args.track_high, low_thr=args.track_low, new_thr=args.track_new, match_thr=args.track_match,
+                       iou2_thr=args.track_iou2, w_iou=args.track_w_iou, max_age=args.track_max_age, match_labels=args.track_labels)
+
+
+def tracked_detections(model, images, texts, test_pipeline, args):
+    """``--track``: the images as one video, ``--track-batch`` frames per ``model.track`` call; yields one host-side
+    ``InstanceData`` per image, filtered like ``inference_detector`` (score, top-k), with ``track_ids`` / ``track_hits``."""
+    params = track_params(args)
+    for i in range(0, len(images), args.track_batch):
+        infos = [test_pipeline(dict(img_id=i + k, img_path=p, texts=texts)) for k, p in enumerate(images[i:i + args.track_batch])]
+        outs = model.track(torch.stack([d["inputs"] for d in infos]), [d["data_samples"] for d in infos], n_seq=1, track_params=params)
+        for o in outs:
+            pred = o.pred_instances
+            pred = pred[pred.scores.float() > args.threshold]
+            if len(pred.scores) > args.topk:
+                pred = pred[pred.scores.float().topk(args.topk)[1]]
+            yield pred.cpu().numpy()
 
 
 def parse_exemplar_boxes(spec: str):
@@ -260,16 +306,23 @@ def main(argv=None, tokenizer=None):
         texts = texts + [[t] for t in ex_names]              # appended after the text classes (their blank class included)
         model.set_text_embeddings(bank, texts)
     results = []
+    tracked = tracked_detections(model, images, texts, test_pipeline, args) if args.track else None
     for n, image_path in enumerate(images):
-        if args.tile > 0:
+        if tracked is not None:
+            pred = next(tracked)
+        elif args.tile > 0:
             pred = tiled_detections(model, image_path, texts, args)
         else:
             pred = inference_detector(model, image_path, texts, test_pipeline, args.topk, args.threshold)
         labels = [f"{texts[c][0]} {s:0.2f}" for c, s in zip(pred["labels"], pred["scores"])]
+        if args.track:
+            labels = [f"#{i} {t}" if i else t for i, t in zip(pred["track_ids"].tolist(), labels)]
         out = osp.join(args.output_dir, osp.basename(image_path))
         visualize(out, image_path, pred["bboxes"], labels)
         if args.dump_json:
             extra = {}
+            if args.track:
+                extra["track_id"] = pred["track_ids"].tolist()
             if args.top_names:                               # per detection: the names of its list, empty slots (label -1) left out
                 extra["names"] = [[[texts[c][0], float(s)] for c, s in zip(cs, ss) if c >= 0]
                                   for cs, ss in zip(pred["top_labels"].tolist(), pred["top_scores"].tolist())]

@@ -15,8 +15,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libwedetect_hip.so")
-SOURCES = ["abi.hip", "conv_gemm.hip", "similarity_grouped.hip", "split_gemm.hip", "split_gemm_pre.hip", "split_gemm_p8.hip", "split_gemm_p4.hip", "split_gemm_conv.hip", "split_gemm_conv3.hip", "split_gemm_mlp.hip", "split_gemm_mlpw.hip", "probe.hip", "stem.hip", "elementwise.hip", "preprocess.hip", "text.hip", "bricks.hip", "evaluate.hip", "det_eval.hip", "postprocess.hip", "feed.hip", "tile.hip", "views.hip", "fold.hip", "best.hip", "sparse.hip", "topn.hip", "groups.hip", "exemplar.hip", "tune.hip"]
-PUBLIC_HEADERS = ["wedetect_hip.h", "wedetect_hip_feed.h", "wedetect_hip_tile.h", "wedetect_hip_views.h", "wedetect_hip_fold.h", "wedetect_hip_best.h", "wedetect_hip_sparse.h", "wedetect_hip_topn.h", "wedetect_hip_groups.h", "wedetect_hip_exemplar.h", "wedetect_hip_tune.h"]
+SOURCES = ["abi.hip", "conv_gemm.hip", "similarity_grouped.hip", "split_gemm.hip", "split_gemm_pre.hip", "split_gemm_p8.hip", "split_gemm_p4.hip", "split_gemm_conv.hip", "split_gemm_conv3.hip", "split_gemm_mlp.hip", "split_gemm_mlpw.hip", "probe.hip", "stem.hip", "elementwise.hip", "preprocess.hip", "text.hip", "bricks.hip", "evaluate.hip", "det_eval.hip", "postprocess.hip", "feed.hip", "tile.hip", "views.hip", "fold.hip", "best.hip", "sparse.hip", "topn.hip", "groups.hip", "exemplar.hip", "tune.hip", "track.hip"]
+PUBLIC_HEADERS = ["wedetect_hip.h", "wedetect_hip_feed.h", "wedetect_hip_tile.h", "wedetect_hip_views.h", "wedetect_hip_fold.h", "wedetect_hip_best.h", "wedetect_hip_sparse.h", "wedetect_hip_topn.h", "wedetect_hip_groups.h", "wedetect_hip_exemplar.h", "wedetect_hip_tune.h", "wedetect_hip_track.h"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-inline-asm",
          "-I", os.path.join(ROOT, "include"), "-I", CSRC]
@@ -63,12 +63,13 @@ NO_SCRATCH = {"stem.hip": ["stem_fused_kernel"], "split_gemm_mlpw.hip": ["fused_
               "topn.hip": ["topn_rows_kernel", "topn_unpack_kernel", "topn_kept_kernel"],
               "groups.hip": ["group_rows_kernel"],
               "exemplar.hip": ["exemplar_assign_kernel", "exemplar_pool_kernel"],
-              "tune.hip": ["tune_targets_kernel", "tune_grad_kernel", "tune_update_kernel"]}
+              "tune.hip": ["tune_targets_kernel", "tune_grad_kernel", "tune_update_kernel"],
+              "track.hip": ["track_step_kernel", "track_reset_kernel", "track_export_kernel"]}
 # (a source listed here with no kernel names gets the hazard scan and its NO_SCRATCH check only: similarity_grouped.hip has no
 # inline asm; its kernel is held to "no scratch" like the GEMM it is built from; feed.hip, tile.hip and views.hip likewise: byte packing in registers)
 ASM_VMEM_SOURCES = {"split_gemm_mlpw.hip": ["fused_mlp_wide_kernel"], "split_gemm_mlp.hip": [], "split_gemm_p8.hip": [],
                     "split_gemm_p4.hip": [], "split_gemm_pre.hip": [], "split_gemm_conv.hip": [], "split_gemm_conv3.hip": [], "stem.hip": [], "elementwise.hip": [], "similarity_grouped.hip": [],
-                    "feed.hip": [], "tile.hip": [], "views.hip": [], "best.hip": [], "sparse.hip": [], "topn.hip": [], "groups.hip": [], "exemplar.hip": [], "tune.hip": []}
+                    "feed.hip": [], "tile.hip": [], "views.hip": [], "best.hip": [], "sparse.hip": [], "topn.hip": [], "groups.hip": [], "exemplar.hip": [], "tune.hip": [], "track.hip": []}
 
 
 # kernels that issue ds_reads from inline asm (invisible to the compiler's waitcnt pass): scripts/check_asm_ds_reads.py

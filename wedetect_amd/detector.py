@@ -772,6 +772,7 @@ class YOLOWorldDetector(_DeviceModule):
         # synonym lists of the class-text files — instead of its first caption (wedetect_amd/groups.py, engine.ImageTower.detect)
         self.prompt_groups = bool(prompt_groups)
         self._tuner = None                                   # tune_bank's cache between fit=False calls (tune.BankTuner)
+        self._tracker = None                                 # track()'s own track.Tracker, made by its first call
         if self.prompt_groups and (best_class or sparse_scores or top_names):
             raise ValueError("prompt_groups=True is a multi-label dense step of its own: it excludes best_class, sparse_scores and top_names")
         self._plans: Dict[Tuple[str, ...], object] = {}      # first captions -> groups.PromptGroups of that bank (prompt_groups only)
@@ -997,6 +998,12 @@ class YOLOWorldDetector(_DeviceModule):
         (uint8 or float 0-255, BGR — DetDataPreprocessor does bgr_to_rgb and /255,
         wedetect_base.py:44-48), all of one shape with H, W multiples of 32 (the test pipeline letterboxes
         to ``img_scale``)."""
+        res, counts, samples = self._predict_step(batch_inputs, batch_data_samples, rescale)
+        return self._instances(res, counts, samples)
+
+    def _predict_step(self, batch_inputs, batch_data_samples, rescale: bool, **over):
+        """The guarded tower step of ``predict`` (``over``: keywords that replace the step's own, e.g. ``with_embed``).  Returns
+        (the tower's result buffers, the counts on the host, the samples as a list)."""
         dev = self._h.device
         if dev is None:
             raise RuntimeError("model is not on a HIP device: call .cuda()")
@@ -1020,7 +1027,13 @@ class YOLOWorldDetector(_DeviceModule):
         tower = self._h.tower(len(xs), hh, ww)
         meta = torch.tensor([letterbox_meta(_meta_of(s), hh, ww, rescale) for s in samples], dtype=torch.float32, device=dev)
         bank, counts_dev = (banks[0].to(dev), None) if packed is None else packed
+        kw.update(over)
         res, counts = self._h.checked_step(tower, x, bank, meta, text_counts=counts_dev, **kw)
+        return res, counts, samples
+
+    def _instances(self, res, counts, samples, extra=()):
+        """``pred_instances`` of every sample from a step's result buffers; ``extra``: (field, [B, max_out] tensor) pairs that are
+        cut to the counts like the others."""
         out = []
         for j, n in enumerate(counts):
             inst = InstanceData(bboxes=res["bboxes"][j, :n].clone(), scores=res["scores"][j, :n].clone(),
@@ -1028,10 +1041,58 @@ class YOLOWorldDetector(_DeviceModule):
             if self.top_names:
                 inst.top_labels = res["top_labels"][j, :n].to(torch.int64)
                 inst.top_scores = res["top_scores"][j, :n].clone()
+            for name, t in extra:
+                setattr(inst, name, t[j, :n].clone())
             s = _as_sample(samples[j])
             s.pred_instances = inst
             out.append(s)
         return out
+
+    # -- tracking ----------------------------------------------------------------------------
+    @torch.no_grad()
+    def track(self, batch_inputs, batch_data_samples, rescale: bool = True, n_seq: int = 1, tracker=None, track_params=None):
+        """``predict`` for the frames of a video, plus persistent ids: ``pred_instances`` gains ``track_ids`` (int32, 0 = the
+        detection belongs to no track) and ``track_hits`` (frames the track was matched in), on the device like the other fields.
+        The batch holds ``n_seq`` independent sequences of ``len(batch) / n_seq`` consecutive frames each, image s * n_frame + f
+        being frame f of sequence s: one video -> ``n_seq=1``, one frame of each of B cameras -> ``n_seq=B``.  The tracks live in
+        ``tracker`` (a ``track.Tracker``; the detector makes and keeps one, with ``track_params`` — a ``track.TrackParams`` — on
+        the first call) and carry over from call to call; ``reset_tracks()`` clears them.
+
+        The association (include/wedetect_hip_track.h: two greedy rounds on IoU and the kept rows' region embeddings) is ONE
+        launch behind the tower step, with no host synchronisation of its own: the step runs with ``with_embed=True`` under the
+        range guard of ``predict``, and the tracker is launched only after the guard has settled the step, so a step that is
+        repeated never reaches the tracks.  Every field ``predict`` fills has the same bits.
+
+        Works with ``best_class`` / ``agnostic_nms``, with ``top_names`` and ``sparse_scores`` (their steps gather the kept rows'
+        embeddings like the default one: the two fall out for free) and with per-image banks.  ``prompt_groups=True`` is refused:
+        its step is not covered by the tracking tests."""
+        from . import track as T
+        if self.prompt_groups:
+            raise NotImplementedError("track with prompt_groups=True is not implemented; use predict, or a detector without groups")
+        n = len(batch_inputs)
+        if isinstance(n_seq, bool) or not isinstance(n_seq, int) or n_seq < 1 or n % n_seq:
+            raise ValueError(f"n_seq must be a positive int that divides the batch of {n} images, got {n_seq!r}")
+        if tracker is None:
+            if self._tracker is not None and self._tracker.n_seq != n_seq:
+                raise ValueError(f"the detector's tracker holds {self._tracker.n_seq} sequences, this call has {n_seq}: call "
+                                 "reset_tracks() first, or pass a tracker")
+            if self._tracker is not None and track_params is not None and track_params != self._tracker.params:
+                raise ValueError("track_params differ from those of the detector's tracker: call reset_tracks() first")
+        elif not isinstance(tracker, T.Tracker) or tracker.n_seq != n_seq or tracker.dim != EMBED_DIM:
+            raise ValueError(f"tracker must be a track.Tracker of {n_seq} sequences and dim {EMBED_DIM}")
+        elif track_params is not None:
+            raise ValueError("track_params belong to the detector's own tracker: a tracker that is passed in carries its own")
+        res, counts, samples = self._predict_step(batch_inputs, batch_data_samples, rescale, with_embed=True)
+        if tracker is None:
+            if self._tracker is None:
+                self._tracker = T.Tracker(n_seq, dim=EMBED_DIM, params=track_params, device=self._h.device)
+            tracker = self._tracker
+        ids, hits = tracker.update(res, n // n_seq)
+        return self._instances(res, counts, samples, (("track_ids", ids), ("track_hits", hits)))
+
+    def reset_tracks(self) -> None:
+        """Forget the tracks of ``track``'s own tracker (ids start at 1 again; the next call may use another ``n_seq``)."""
+        self._tracker = None
 
     # -- exemplar prompts --------------------------------------------------------------------
     @torch.no_grad()
