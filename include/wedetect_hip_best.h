@@ -66,6 +66,8 @@ int wd_best_abi_version(void);
  * multiple of eight rows, so that the eight-row groups the kernel fetches stay inside the padded bank.
  *
  * Extents: reads e_split rows [0, round_up(rows, 8)), t_split rows [0, round_up(n_cls, 8)); writes key[0, rows) only.
+ * Both operands are addressed with 32-bit byte offsets (hence the limit above, and round_up(rows, 8) * dim * 4 < 2^32:
+ * WD_ERR_UNSUPPORTED), key with 64-bit ones; a class index is a 31-bit int.
  * WD_ERR_BAD_ARG: null pointers, non-positive sizes, cls_offset < 0, cls_offset + n_cls > 2^31 - 1, a misaligned key, bad seg
  * arguments.  WD_ERR_UNSUPPORTED: dim % 32, operands not 16-byte aligned, the limit above.
  * ------------------------------------------------------------------------------------------- */

@@ -46,6 +46,13 @@ int wd_fold_abi_version(void);
  *   w_unscale_dev    device float, read by the kernel
  * Extents: reads the batch * hin * win rows of lda floats of p->a, the round_up(n, 8) rows of w_split and of p->bias, one float
  * at w_unscale_dev; writes columns < n of the m mapped output rows only.
+ * Address widths, here and for wd_conv_gemm / wd_conv_gemm_split (whose own header, wedetect_hip.h, is frozen at ABI 15 and
+ * says "lda >= cin" only): rows of a, c, res and c2 are addressed with 64-bit offsets, so m * lda, m * ldc, m * ldres, m * ldc2
+ * and batch * c_batch_stride * ldc may pass 2^31 and 2^32 bytes.  Two limits, both WD_ERR_UNSUPPORTED: the forced tiles cfg 64 /
+ * 65 / 66 of wd_conv_gemm_split need m * lda * 4 < 2^32 and n * round_up(k, 16) * 4 < 2^32 (32-bit operand offsets; cfg < 0
+ * never picks them beyond that), and a kh x kw layer on pre-split activations (WD_SPLIT_A), the row-sharing 3 x 3 kernels
+ * included, needs ((kh - 1) * win + kw - 1) * lda * 4 + cin * 4 <= 2^31 (a filter tap's byte offset from its pixel is a 32-bit
+ * int; a 1 x 1 layer such as this entry's is never refused by it).
  */
 int wd_fold_similarity(const WdConvGemm* p, const void* w_split, float w_unscale, const float* w_unscale_dev, void* stream);
 

@@ -66,6 +66,8 @@ int wd_groups_abi_version(void);
  * Extents: reads e_split rows [0, round_up(rows, 8)), t_split rows [0, n_cls), group_of[cls_offset, cls_offset + n_cls),
  * bin_first[cls_offset / 32, (cls_offset + n_cls) / 32]; writes out[r][g] for r < rows and g in the column range above only
  * (every such element, exactly once; nothing between n_groups and ldo).
+ * Both operands are addressed with 32-bit byte offsets (hence the limit above, and round_up(rows, 8) * dim * 4 < 2^32:
+ * WD_ERR_UNSUPPORTED), out with 64-bit ones (rows * ldo may pass 2^32 bytes); a class index is a 31-bit int.
  * WD_ERR_BAD_ARG: null pointers (the tables included), non-positive sizes, cls_offset < 0 or cls_offset % 32, n_cls % 32,
  * cls_offset + n_cls > 2^31 - 1, n_groups <= 0, ldo < n_groups, out / group_of / bin_first not 4-byte aligned, bad seg arguments.
  * WD_ERR_UNSUPPORTED: dim % 32, operands not 16-byte aligned, the limit above.

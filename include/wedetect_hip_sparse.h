@@ -70,6 +70,8 @@ int wd_sparse_abi_version(void);
  *
  * Extents: reads e_split rows [0, round_up(rows, 8)), t_split rows [0, round_up(n_cls, 8)); reads and writes state[0, 2 * batch);
  * writes list[b][s] for s < min(state[b][0], list_cap) only.
+ * Both operands are addressed with 32-bit byte offsets (hence the limit above, and round_up(rows, 8) * dim * 4 < 2^32:
+ * WD_ERR_UNSUPPORTED); the flat index anchor * n_cls_total + class of a candidate is a 31-bit int (the limit below).
  * WD_ERR_BAD_ARG: null pointers, non-positive sizes, rows % rows_per_img, cls_offset < 0, cls_offset + n_cls > n_cls_total, a
  * misaligned list (8 bytes) or state (4 bytes), a list_cap that is not a power of two or lies outside [1, 2^20], bad seg
  * arguments.  WD_ERR_UNSUPPORTED: rows_per_img * n_cls_total >= 2^31, dim % 32, operands not 16-byte aligned, the limit above.

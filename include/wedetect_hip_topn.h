@@ -69,6 +69,8 @@ int wd_topn_abi_version(void);
  *
  * Extents: reads e_split rows [0, round_up(rows, 8)), t_split rows [0, round_up(n_cls, 8)), row_scale / row_bias [0, rows);
  * reads and writes key[0, rows * n_top) only.
+ * Both operands are addressed with 32-bit byte offsets (hence the limit above, and round_up(rows, 8) * dim * 4 < 2^32:
+ * WD_ERR_UNSUPPORTED), key with 64-bit ones; a class index is a 31-bit int.
  * WD_ERR_BAD_ARG: null pointers, non-positive sizes, n_top outside 1 .. 8, cls_offset < 0, cls_offset + n_cls > 2^31 - 1,
  * rows * n_top > 2^31 - 16, a misaligned key, bad seg arguments, only one of row_scale / row_bias, the row affine together with
  * seg_rows > 0.  WD_ERR_UNSUPPORTED: dim % 32, operands not 16-byte aligned, the limit above.

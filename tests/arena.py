@@ -86,7 +86,8 @@ class Arena:
     # ---------------------------------------------------------------------------------------------- allocation
     def take(self, name: str, shape, dtype: torch.dtype = torch.float32, *, ld: Optional[int] = None, align: int = 256,
              misalign: int = 0, role: str = "output", fillers: Sequence[int] = (), fill: Optional[int] = None,
-             data: Optional[torch.Tensor] = None, batch_stride: Optional[int] = None, row_pitch: Optional[int] = None) -> torch.Tensor:
+             data: Optional[torch.Tensor] = None, batch_stride: Optional[int] = None, row_pitch: Optional[int] = None,
+             guard_bytes: Optional[int] = None) -> torch.Tensor:
         """A view of ``shape`` / ``dtype`` whose rows (the last dimension) are ``ld`` elements apart (default: dense).
 
         ``batch_stride`` (3-d shapes [B, R, C] only): image b starts ``batch_stride`` ROWS after image b - 1 (the
@@ -97,7 +98,11 @@ class Arena:
         buffer use ``ALT_PATTERN`` instead, so that a stray filler store still differs from the guard.  ``fill``: byte the
         payload starts with (default: the guard pattern); ``data``: initial contents (copied into the view).
         ``row_pitch`` (1-d byte blobs such as a split weight buffer or a workspace): bytes of one logical row of what the
-        blob holds, for sizing the guard (256 rows of it); a 1-d buffer without it gets the 64 KiB minimum."""
+        blob holds, for sizing the guard (256 rows of it); a 1-d buffer without it gets the 64 KiB minimum.
+        ``guard_bytes``: the guard on each side in bytes (rounded up to 256) INSTEAD of the default — wider where the case watches
+        for far strays (tests/test_gpu_offsets.py: 2 GiB, so that an address wrapped at 2^31 or 2^32 still lands in memory the
+        arena owns), or narrower where 256 rows of a very wide pitch would not fit a device.  Guards of that size are checked
+        with :meth:`check_blocked`."""
         if role not in ROLES:
             raise ValueError(f"role must be one of {ROLES}")
         if name in self.buffers:
@@ -140,6 +145,10 @@ class Arena:
             row_idx = row_idx[..., None] + torch.arange(d, dtype=torch.int64) * st
         row_off = (row_idx.reshape(-1) * esz).to(self.device)
         guard = max(GUARD_MIN_BYTES, GUARD_MIN_ROWS * (pitch if len(shape) > 1 else int(row_pitch or 0)))
+        if guard_bytes is not None:
+            if guard_bytes < 0:
+                raise ValueError(f"{name}: guard_bytes {guard_bytes} < 0")
+            guard = int(guard_bytes)
         guard = (guard + 255) // 256 * 256
         start = self._top + guard
         start += (misalign - (start - self._base)) % align
@@ -249,6 +258,77 @@ class Arena:
                     out.append(dict(buffer=buf.name, side="input changed", first=(int(first[0]), int(first[1])),
                                     last=(int(last[0]), int(last[1])), count=int(bad.shape[0])))
         return out
+
+    # ---------------------------------------------------------------------------------------------- multi-GiB arenas
+    def _scan(self, lo: int, hi: int, pattern: int, block: int) -> Optional[int]:
+        """Arena offset of the first byte of [lo, hi) that differs from ``pattern`` (None: clean), ``block`` bytes at a time."""
+        for a in range(lo, hi, block):
+            chunk = self.mem[a:min(a + block, hi)]
+            head = (-a) % 8                                   # whole 8-byte words in the middle: an eighth of the elements
+            if chunk.numel() >= 64 and (chunk.data_ptr() + head) % 8 == 0:
+                body = chunk[head:head + (chunk.numel() - head) // 8 * 8].view(torch.int64)
+                word = int.from_bytes(bytes([pattern]) * 8, "little", signed=True)
+                if bool((body == word).all()) and bool((chunk[:head] == pattern).all()) and \
+                        bool((chunk[head + body.numel() * 8:] == pattern).all()):
+                    continue
+            elif bool((chunk == pattern).all()):
+                continue
+            return a + int((chunk != pattern).nonzero()[0])
+        return None
+
+    def violations_blocked(self, block_bytes: int = 256 << 20) -> List[dict]:
+        """What :meth:`violations` reports — guards, spare columns, rows between images, changed inputs — found without index or
+        mask tensors of the arena's size: guards and gaps are walked ``block_bytes`` at a time, spare columns as strided views over
+        blocks of rows.  For arenas of several GiB, where the masks of :meth:`violations` would not fit beside the arena.  One
+        record per buffer and side, with the first offending byte only (``count`` is 1: the walk stops there)."""
+        out = []
+        for buf in self.buffers.values():
+            def rec(side, first):
+                out.append(dict(buffer=buf.name, side=side, first=first, last=first, count=1))
+            bad = self._scan(buf.start - buf.guard, buf.start, buf.pattern, block_bytes)
+            if bad is not None:                               # the LAST bad byte is the nearest; report the first found, as a distance
+                rec("low guard", buf.start - bad)
+            bad = self._scan(buf.end, buf.end + buf.guard, buf.pattern, block_bytes)
+            if bad is not None:
+                rec("high guard", bad - buf.end + 1)
+            if buf.rows > 1:
+                off = buf.row_off[:buf.rows].cpu()
+                step = off[1:] - off[:-1]
+                cut = (step != buf.pitch).nonzero().flatten().tolist()            # rows after which the pitch is irregular
+                spare = buf.pitch - buf.row_bytes
+                r0 = 0
+                for r1 in cut + [buf.rows - 1]:                                   # rows r0 .. r1 are one pitch apart
+                    n = r1 - r0                                                   # spare runs behind rows r0 .. r1 - 1
+                    per = max(1, block_bytes // max(spare, 1))
+                    for a in range(0, n if spare else 0, per):
+                        k = min(per, n - a)
+                        base = buf.start + int(off[r0 + a]) + buf.row_bytes
+                        v = self.mem.as_strided((k, spare), (buf.pitch, 1), base + self.mem.storage_offset())
+                        if not bool((v == buf.pattern).all()):
+                            rc = (v != buf.pattern).nonzero()[0]
+                            rec("spare columns", (r0 + a + int(rc[0]), int(rc[1]) + 1))
+                            break
+                    if r1 < buf.rows - 1:                                         # the gap up to the next run (rows between images)
+                        lo = buf.start + int(off[r1]) + buf.row_bytes
+                        bad = self._scan(lo, buf.start + int(off[r1 + 1]), buf.pattern, block_bytes)
+                        if bad is not None:
+                            rec("spare columns", (r1, bad - lo + 1))
+                    r0 = r1 + 1
+            if buf.snapshot is not None:
+                diff = (self._get(buf) != buf.snapshot).nonzero()
+                if diff.shape[0]:
+                    first = diff[0]
+                    rec("input changed", (int(first[0]), int(first[1])))
+        return out
+
+    def check_blocked(self, block_bytes: int = 256 << 20) -> None:
+        if not self.armed:
+            raise RuntimeError("check_blocked() without arm()")
+        v = self.violations_blocked(block_bytes)
+        if v:
+            lines = [f"{r['buffer']}: {r['side']}: first offending byte at {r['first']}" for r in v]
+            raise GuardViolation("memory touched outside the documented extents (guards: 1-based distance from the payload "
+                                 "edge; spare columns: (row, bytes past the row's end); inputs: (row, byte)):\n  " + "\n  ".join(lines))
 
     def check(self) -> None:
         if not self.armed:

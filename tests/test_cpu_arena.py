@@ -169,6 +169,47 @@ def test_shrunk_extent_reports_legitimate_stores_at_the_edge():
     assert _one(ar) == dict(buffer="w", side="high guard", first=1, last=16, count=16)
 
 
+def test_guard_bytes_widens_the_guard_and_the_blocked_walk_finds_what_the_mask_finds():
+    """The guard-size parameter of the large-offset tests (tests/test_gpu_offsets.py: 2 GiB per side there, 1 MiB here) and the
+    block-wise check that goes with it: the same stores, found at the same places as by violations(), with blocks far smaller
+    than the buffers and not aligned to anything."""
+    ar = _arena(0xFF, cap=16 << 20)
+    x = ar.take("x", (9, 10), ld=16, role="input", guard_bytes=1 << 20, data=torch.ones(9, 10))
+    ar.take("small", (4, 8), guard_bytes=100)                                 # the caller's figure stands, rounded up to 256
+    ar.take("img", (3, 4, 6), ld=8, batch_stride=7, misalign=16, guard_bytes=(1 << 20) + 1)
+    b, bs, bi = ar.buffers["x"], ar.buffers["small"], ar.buffers["img"]
+    assert b.guard == 1 << 20 and bs.guard == 256 < GUARD_MIN_BYTES and bi.guard == (1 << 20) + 256 and (bi.start - ar._base) % 256 == 16
+    assert bs.start - bs.guard >= b.end + b.guard and bi.start - bi.guard >= bs.end + bs.guard
+    with pytest.raises(ValueError):
+        ar.take("neg", (4,), guard_bytes=-1)
+    with pytest.raises(RuntimeError):
+        ar.check_blocked()
+    ar.arm()
+    for blk in (1 << 30, 4096, 1001):
+        ar.check_blocked(blk)
+        assert ar.violations_blocked(blk) == []
+    stores = [(b.start - (1 << 20), dict(buffer="x", side="low guard", first=1 << 20)),
+              (b.end + (1 << 20) - 1, dict(buffer="x", side="high guard", first=1 << 20)),
+              (b.start + 3 * b.pitch + b.row_bytes + 2, dict(buffer="x", side="spare columns", first=(3, 3))),
+              (bi.start + 4 * bi.pitch, dict(buffer="img", side="spare columns", first=(3, 32 - 24 + 1))),      # first row between two images
+              (bi.start + 7 * bi.pitch - 1, dict(buffer="img", side="spare columns", first=(3, 3 * 32 + 8))),       # last byte before image 1
+              (bi.start + (7 + 2) * bi.pitch + bi.row_bytes, dict(buffer="img", side="spare columns", first=(6, 1)))]
+    for at, want in stores:
+        keep = int(ar.mem[at])
+        ar.mem[at] = 0x5A
+        full = _one(ar)
+        for blk in (1 << 30, 1001):
+            got = ar.violations_blocked(blk)
+            assert len(got) == 1 and {k: got[0][k] for k in want} == want, (at, blk, got)
+            assert (full["buffer"], full["side"], full["first"]) == (want["buffer"], want["side"], want["first"])
+        with pytest.raises(GuardViolation, match=want["buffer"] + ": " + want["side"]):
+            ar.check_blocked(1001)
+        ar.mem[at] = keep
+    x[8, 9] = 2.0
+    got = ar.violations_blocked(1001)
+    assert len(got) == 1 and got[0]["side"] == "input changed" and got[0]["first"][0] == 8 and 36 <= got[0]["first"][1] < 40
+
+
 # ------------------------------------------------------------------------------------------ coverage of the C ABI
 # The closed set the extent tests may leave out: functions without device memory and the two diagnostics.  wd_recall_scratch_floats
 # and wd_topk_capacity are pointer-free size queries like the *_bytes family (their names just do not end in _bytes); the

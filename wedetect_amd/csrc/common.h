@@ -85,6 +85,15 @@ static inline bool wd_similarity_bank_fits(int32_t n_cls, int32_t dim) {
   return (unsigned long long)((n_cls + 7) & ~7) * (unsigned long long)((dim + 15) / 16 * 16) * 4ull < (1ull << 32);
 }
 
+// The 256 x 256 and 128 x 256 pre-split kernels (split_gemm_p8.hip, split_gemm_p4.hip; cfg 64 / 65 / 66) address BOTH operands with
+// 32-bit byte offsets from their bases: a_rows rows of lda fp32 words and w_rows rows of k16 fp16 hi/lo pairs must each end below
+// 2^32 bytes.  Their launchers refuse anything else (WD_ERR_UNSUPPORTED); production dispatch (split_gemm.hip) asks first and
+// falls back to the direct-to-LDS kernels (cfg 60 / 63), whose per-lane pointers are 64-bit.
+static inline bool wd_dma32_fits(long long a_rows, int lda, long long w_rows, int k16) {
+  return (unsigned long long)a_rows * (unsigned long long)lda * 4ull < (1ull << 32) &&
+         (unsigned long long)w_rows * (unsigned long long)k16 * 4ull < (1ull << 32);
+}
+
 __device__ __forceinline__ float wd_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
 // GEMM-epilogue variant: hardware exp2 / rcp (<= 2 ulp, i.e. <= 1.2e-7 absolute on a score), a third of the
 // instructions of the exact form — the similarity GEMM's epilogue is 20 sigmoids per lane

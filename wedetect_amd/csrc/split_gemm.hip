@@ -271,9 +271,13 @@ static int conv_gemm_split_impl(const WdConvGemm* pp, const void* w_split, float
     // shipped towers; other widths still work, with padding).  Plain layers go global -> LDS
     // directly (cfg 60 / 63); the 2x2 downsample conv and odd K keep the register-staged kernels.
     // long-m layers (ConvNeXt stages 1-2): the ping-pong 256 x 128 kernel, else 128 x 128
-    if (production && plain && !special && p.k % 16 == 0)
+    if (production && plain && !special && p.k % 16 == 0) {
       cfg = pick_presplit_cfg(p.m, p.n, p.k, ws != nullptr && force_splits == 0 && ws_bytes / 4 >= wd_p8_workspace_floats() &&
                                                  p.lda % 8 == 0 && !(flags & ~(WD_SPLIT_A | WD_SPLIT_C)));
+      // the choice above goes by shape; cfg 64 / 65 / 66 also have a size limit (32-bit operand offsets, wd_dma32_fits) that a wide
+      // lda or a very long m exceeds: such a layer takes what pick_presplit_cfg gives every shape those kernels do not cover
+      if (cfg >= 64 && !wd_dma32_fits(p.m, p.lda, p.n, (p.k + 15) / 16 * 16)) cfg = p.m >= 131072 ? 63 : 60;
+    }
     if (cfg != 50 && cfg != 51 && cfg != 55 && cfg != 60 && cfg != 63 && cfg != 64 && cfg != 65 && cfg != 66 && !(cfg >= 640 && cfg < 768)) cfg = 51;
     if ((flags & WD_SPLIT_C) && cfg == 55) cfg = 50;
   }

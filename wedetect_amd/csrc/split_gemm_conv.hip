@@ -350,6 +350,13 @@ bool wd_conv_pp_ok(const WdConvGemm& p, int flags) {
     return false;                                     // (c_batch_stride: c2 takes c's row mapping, split_epi_oct.h)
   if ((flags & WD_SPLIT_C) ? (p.ldc % 8 != 0) : (p.ldc % 4 != 0 && !ragged_ok)) return false;
   if (p.out_mode == WD_OUT_DECONV2X2 && (p.n % 32)) return false;
+  // the stage cursor adds the filter tap's byte offset ((kh * win + kw) * lda + ci) * 4 to the pixel's 64-bit address as an int:
+  // the last tap's last channel chunk must end at or below 2^31 bytes (a 1 x 1 layer: cin * 4, i.e. always).  The row-sharing
+  // 3 x 3 kernels (split_gemm_conv3.hip) run only where this function agrees too (split_gemm.hip) and their own int offset,
+  // ((kh - 1) * wout * lda + ci) * 4 with kh = 0 .. 2, is at most half of this one: they inherit the limit
+  if ((unsigned long long)((long long)(p.kh - 1) * p.win + (p.kw - 1)) * (unsigned long long)p.lda * 4ull + (unsigned long long)p.cin * 4ull >
+      (1ull << 31))
+    return false;
   return true;
 }
 

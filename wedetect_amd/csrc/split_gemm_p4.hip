@@ -273,8 +273,7 @@ int launch_p4(const WdConvGemm& p, const void* wsp, float unscale, hipStream_t s
   const long long nblk = (long long)nbm * nbn;
   if (nblk <= 0 || nblk > 0x7fffffffLL) return WD_ERR_BAD_ARG;
   const int k16 = (p.k + 15) / 16 * 16;
-  if ((unsigned long long)p.m * p.lda * 4 >= (1ull << 32) || (unsigned long long)p.n * k16 * 4 >= (1ull << 32))
-    return WD_ERR_UNSUPPORTED;                                     // 32-bit DMA offsets from the operand bases
+  if (!wd_dma32_fits(p.m, p.lda, p.n, k16)) return WD_ERR_UNSUPPORTED;   // 32-bit DMA offsets from the operand bases
   const int vec_c = (p.ldc % 4 == 0) && wd_aligned16(p.c);
   const int vec_res = p.res ? ((p.ldres % 4 == 0) && wd_aligned16(p.res)) : 0;
   const int vec_bias = p.bias ? wd_aligned16(p.bias) : 0;
