@@ -480,7 +480,7 @@ class Tracker:
         return ret
 
 
-def _bind(real, args, kwargs):
+def _arguments(real, args, kwargs):
     ba = inspect.signature(real).bind(*args, **kwargs)
     ba.apply_defaults()
     return SimpleNamespace(**ba.arguments)
@@ -533,7 +533,7 @@ def track(names=None, stream_names=None, ignore_wait=None, audit=False):
         def recording(*args, **kwargs):
             tr._hold_tree(args)
             tr._hold_tree(kwargs)
-            a = _bind(real, args, kwargs)
+            a = _arguments(real, args, kwargs)
             tr.inside += 1
             try:
                 if audit:

@@ -4,15 +4,13 @@ every entry point of include/wedetect_hip.h that takes device memory has a case 
 The "stray stores" below are ordinary torch indexing inside the arena's own allocation: no kernel is built to misbehave and
 nothing is written outside an allocation."""
 import fnmatch
-import os
 import re
 
 import pytest
 import torch
 
+from tests.abi_decl import declared
 from tests.arena import ALT_PATTERN, GUARD_MIN_BYTES, Arena, GuardViolation, pattern_value
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _arena(pattern=0x00, cap=8 << 20):
@@ -218,24 +216,18 @@ EXEMPT_ALLOWED = ("wd_abi_version", "wd_strerror", "wd_sizeof_*", "*_bytes", "*_
                   "wd_probe_lds_dma", "wd_probe_issue", "wd_recall_scratch_floats", "wd_topk_capacity")
 
 
-def _declared():
-    """name -> parameter list of every wd_* function the header declares."""
-    hdr = open(os.path.join(ROOT, "include", "wedetect_hip.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    return {m.group(1): m.group(2) for m in re.finditer(r"\b(wd_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", hdr)}
-
-
-def _takes_memory(params: str) -> bool:
-    """A pointer parameter other than the stream handle (the WdConvGemm description counts: it carries device pointers)."""
-    return any("*" in p and not re.search(r"\bvoid\s*\*\s*stream$", p.strip()) for p in params.split(","))
+def _takes_memory(proto) -> bool:
+    """A pointer parameter other than the stream handle (the WdConvGemm description counts: it carries device pointers).
+    ``proto``: a (return type, [parameter strings]) entry of ``abi_decl.declared``."""
+    return any("*" in p and not re.search(r"\bvoid\s*\*\s*stream$", p) for p in proto[1])
 
 
 def test_every_entry_point_with_device_memory_has_an_extents_case():
     from tests.test_gpu_extents import CASES, EXEMPT
-    decl = _declared()
+    decl = declared("wedetect_hip.h")
     assert len(decl) >= 55 and {"wd_conv_gemm", "wd_topk_candidates", "wd_det_match", "wd_stem_fused"} <= set(decl)
     covered = {c.entry for c in CASES}
-    for name, params in sorted(decl.items()):
+    for name in sorted(decl):
         assert name in covered or name in EXEMPT, f"{name}: new ABI entry without a case in tests/test_gpu_extents.py (or an EXEMPT reason)"
         assert not (name in covered and name in EXEMPT), f"{name}: both covered and exempt"
     for name, reason in EXEMPT.items():

@@ -124,12 +124,14 @@ def test_keywords_reach_the_detector_from_a_config_and_from_the_scripts():
 
 
 def test_header_entry_list_matches_the_binding_and_every_entry_has_an_extent_case():
+    from tests.abi_decl import declared
+    from tests.test_cpu_abi import check_header
     from wedetect_amd import best as BS
     from wedetect_amd import build as WB
     hdr = open(os.path.join(ROOT, "include", "wedetect_hip_best.h")).read()
-    body = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    names = re.findall(r"^\s*(?:int|int32_t|int64_t)\s+(wd_\w+)\s*\(", body, flags=re.M)
-    assert sorted(names) == sorted(BS.EXPORTS) and len(set(names)) == len(names)
+    names = list(declared("wedetect_hip_best.h"))
+    assert sorted(names) == sorted(BS.EXPORTS)
+    check_header("wedetect_hip_best.h")                       # argtypes / restype against the prototypes
     assert "wedetect_hip_best.h" in WB.PUBLIC_HEADERS and "best.hip" in WB.SOURCES
     assert re.search(r"#define\s+WD_NMS_MMCV_AGNOSTIC\s+3\b", hdr) and BS.NMS_MMCV_AGNOSTIC == 3
     assert BS.LIB.wd_best_abi_version() == BS.BEST_ABI_VERSION == 1

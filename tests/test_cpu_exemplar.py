@@ -10,16 +10,12 @@ import pytest
 
 import tests.exemplar_hazards  # noqa: F401  (declares the wrappers of wedetect_amd/exemplar.py to tests/hazards.py)
 from tests import exemplar_ref as R
+from tests.abi_decl import declared
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "wedetect_hip_exemplar.h")
 f32 = np.float32
 IDENT = np.array([[0, 0, 0, 1, 1, 64, 64, 0]], f32)
-
-
-def _declared():
-    hdr = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    return {m.group(1): m.group(2) for m in re.finditer(r"\b(wd_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", hdr)}
 
 
 # ------------------------------------------------------------------------------------------------------------ reference
@@ -99,11 +95,12 @@ def test_pool_slot_order_support_and_empty_classes():
 
 # ------------------------------------------------------------------------------------------------- header, library, build
 def test_library_exports_the_header_and_the_frozen_abi_is_untouched():
+    from tests.test_cpu_abi import check_header
     from tests.test_cpu_tile import MAIN_HEADER_SHA256
     from wedetect_amd import build as WB
     from wedetect_amd import exemplar as EX
     from wedetect_amd import lib as L
-    decl = _declared()
+    decl = declared("wedetect_hip_exemplar.h")
     assert sorted(decl) == sorted(EX.EXPORTS) == ["wd_exemplar_abi_version", "wd_exemplar_assign", "wd_exemplar_pool"]
     for name in decl:
         assert hasattr(L.LIB, name)
@@ -113,12 +110,10 @@ def test_library_exports_the_header_and_the_frozen_abi_is_untouched():
     hdr = open(HEADER).read()
     assert re.search(r"#define\s+WD_EXEMPLAR_MAX_M\s+8\b", hdr) and EX.MAX_M == 8
     assert re.search(r"#define\s+WD_EXEMPLAR_MAX_EX\s+64\b", hdr) and EX.MAX_EX == 64
-    conv = {"int32_t": ctypes.c_int32, "float": ctypes.c_float}
-    for name, params in decl.items():
+    check_header("wedetect_hip_exemplar.h")                                   # argtypes / restype against the prototypes
+    for name in decl:
         if name == "wd_exemplar_abi_version":
             continue
-        want = [ctypes.c_void_p if "*" in p else conv[p.split()[0]] for p in (" ".join(q.split()) for q in params.split(","))]
-        assert list(getattr(EX.LIB, name).argtypes) == want, name
         doc = hdr[: hdr.index(f"int {name}(")].rsplit("/* ----", 1)[1]
         assert "Extents:" in doc and "WD_ERR_BAD_ARG:" in doc, name
 
@@ -169,7 +164,7 @@ def test_argument_refusals_before_any_launch():
 def test_every_exemplar_entry_point_with_device_memory_has_an_extents_case():
     from tests.test_cpu_arena import _takes_memory
     from tests.test_gpu_exemplar_extents import CASES
-    decl = _declared()
+    decl = declared("wedetect_hip_exemplar.h")
     covered = {c.entry for c in CASES}
     for name, params in sorted(decl.items()):
         if name == "wd_exemplar_abi_version":

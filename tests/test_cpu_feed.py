@@ -6,7 +6,6 @@ import fnmatch
 import hashlib
 import importlib.util
 import os
-import re
 import sys
 
 import numpy as np
@@ -17,23 +16,18 @@ ROOT = os.path.dirname(HERE)
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-FEED_HEADER = os.path.join(ROOT, "include", "wedetect_hip_feed.h")
+from tests.abi_decl import declared  # noqa: E402
+
+FEED_HEADER = "wedetect_hip_feed.h"
 # sha256 of include/wedetect_hip.h at ABI 15: the feed lives in a header of its own, the frozen one does not move
 MAIN_HEADER_SHA256 = "2b62a824664907f02d66fef8abe43f4c50fa0703c00814e15a08129143937784"
-
-
-def _declared():
-    """name -> parameter list of every wd_* function the feed header declares."""
-    hdr = open(FEED_HEADER).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    return {m.group(1): m.group(2) for m in re.finditer(r"\b(wd_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", hdr)}
 
 
 # ------------------------------------------------------------------------------------------ library and header
 def test_library_exports_the_feed_header_and_the_frozen_abi_is_untouched():
     from wedetect_amd import build as wb
     wb.build(verbose=False)
-    decl = set(_declared())
+    decl = set(declared(FEED_HEADER))
     assert {"wd_feed_abi_version", "wd_feed_sizeof_image", "wd_feed_batch_u8", "wd_feed_tmp_bytes"} <= decl
     lib = ctypes.CDLL(wb.LIB)
     missing = [s for s in sorted(decl) if not hasattr(lib, s)]
@@ -57,10 +51,10 @@ def test_library_exports_the_feed_header_and_the_frozen_abi_is_untouched():
 def test_every_feed_entry_point_with_device_memory_has_an_extents_case():
     from tests.test_cpu_arena import EXEMPT_ALLOWED, _takes_memory
     from tests.test_gpu_feed_extents import CASES, EXEMPT
-    decl = _declared()
+    decl = declared(FEED_HEADER)
     covered = {c.entry for c in CASES}
     allowed = EXEMPT_ALLOWED + ("wd_feed_abi_version", "wd_feed_sizeof_*")
-    for name, params in sorted(decl.items()):
+    for name in sorted(decl):
         assert name in covered or name in EXEMPT, f"{name}: feed entry without a case in tests/test_gpu_feed_extents.py (or an EXEMPT reason)"
         assert not (name in covered and name in EXEMPT), f"{name}: both covered and exempt"
     for name, reason in EXEMPT.items():

@@ -1,13 +1,8 @@
 """The text bank folded into the head's embedding conv, on the CPU: the algebra of the fold against the oracle in float64
 (before any kernel is involved), and the C ABI of include/wedetect_hip_fold.h."""
-import os
-import re
-
 import numpy as np
 import torch
 import torch.nn.functional as F
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _c2_of_level(sd, l, feat):
@@ -85,13 +80,12 @@ def test_scores_from_c2_with_folded_weights_equal_the_oracle_head_in_float64():
 
 
 def test_library_exports_the_fold_header_and_every_memory_entry_has_an_extents_case():
+    from tests.abi_decl import declared
     from tests.test_cpu_arena import _takes_memory
     from tests.test_gpu_fold_extents import CASES, EXEMPT
     from wedetect_amd import build as wb
     from wedetect_amd import fold as FD
-    hdr = open(os.path.join(ROOT, "include", "wedetect_hip_fold.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    decl = {m.group(1): m.group(2) for m in re.finditer(r"\b(wd_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", hdr)}
+    decl = declared("wedetect_hip_fold.h")
     assert set(decl) == set(FD.EXPORTS)
     assert "wedetect_hip_fold.h" in wb.PUBLIC_HEADERS and "fold.hip" in wb.SOURCES
     assert FD.LIB.wd_fold_abi_version() == FD.FOLD_ABI_VERSION == 1

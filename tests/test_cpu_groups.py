@@ -190,31 +190,20 @@ def test_keyword_reaches_the_detector_from_a_config_and_from_both_scripts(capsys
     assert "sum(len(t) for t in texts) if args.prompt_groups" in src
 
 
-def _c_to_ctypes(decl: str):
-    import ctypes as C
-    out = []
-    for arg in [a.strip() for a in decl.split(",")]:
-        if "*" in arg:
-            out.append(C.POINTER(C.c_float) if re.match(r"const float\*\s*seg_", arg) else C.c_void_p)
-        else:
-            out.append({"int32_t": C.c_int32, "int64_t": C.c_int64, "float": C.c_float}[arg.split()[0]])
-    return out
-
-
 def test_header_prototypes_match_the_binding_and_every_entry_has_an_extent_case():
+    from tests.abi_decl import declared
+    from tests.test_cpu_abi import check_header
     from wedetect_amd import best, fold, sparse, topn
     from wedetect_amd import build as WB
     from wedetect_amd import groups as PG
     from wedetect_amd import lib as L
     hdr = open(os.path.join(ROOT, "include", "wedetect_hip_groups.h")).read()
-    body = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    protos = {m.group(1): m.group(2) for m in re.finditer(r"^\s*int\s+(wd_\w+)\s*\(([^)]*)\)\s*;", body, flags=re.M)}
+    protos = declared("wedetect_hip_groups.h")
     assert sorted(protos) == sorted(PG.EXPORTS) == ["wd_group_rows", "wd_group_similarity_split", "wd_groups_abi_version"]
+    assert all(ret == "int" for ret, _ in protos.values())
     assert "wedetect_hip_groups.h" in WB.PUBLIC_HEADERS and "groups.hip" in WB.SOURCES
     assert WB.NO_SCRATCH["groups.hip"] == ["group_rows_kernel"] and "split_gemm_p8_kernel" in WB.NO_SCRATCH["split_gemm_p8.hip"]
-    for name, decl in protos.items():
-        if name != "wd_groups_abi_version":
-            assert list(getattr(PG.LIB, name).argtypes) == _c_to_ctypes(" ".join(decl.split())), name
+    check_header("wedetect_hip_groups.h")                     # argtypes / restype against the prototypes
     assert re.search(r"#define\s+WD_GROUP_BIN\s+32\b", hdr) and PG.BIN == 32
     assert PG.LIB.wd_groups_abi_version() == PG.GROUPS_ABI_VERSION == 1
     assert L.LIB.wd_abi_version() == L.ABI_VERSION == 15       # the main ABI and the other add-on headers stay

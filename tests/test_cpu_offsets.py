@@ -203,26 +203,16 @@ HEADERS = ("wedetect_hip.h", "wedetect_hip_best.h", "wedetect_hip_topn.h", "wede
 ADDRESSING = re.compile(r"^(ld\w*|\w*stride\w*|rows|rows_per_img|n_per_image|cls_offset)$")
 
 
-def _declared():
-    """name -> parameter names of every wd_* function of the five headers."""
-    out = {}
-    for h in HEADERS:
-        hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", h)).read(), flags=re.S)
-        for m in re.finditer(r"\b(wd_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", hdr):
-            params = [p.strip() for p in m.group(2).split(",") if p.strip() and p.strip() != "void"]
-            out[m.group(1)] = params
-    return out
-
-
-def _addresses_by_argument(params) -> bool:
+def _addresses_by_argument(proto) -> bool:
     """A stride, row-count or class-offset parameter, or the WdConvGemm description (which carries lda / ldc / ldres / ldc2 /
     c_batch_stride) — of a function that takes device memory (size queries address nothing)."""
     from tests.test_cpu_arena import _takes_memory
-    return _takes_memory(", ".join(params)) and any("WdConvGemm" in p or ADDRESSING.match(p.split()[-1].lstrip("*")) for p in params)
+    return _takes_memory(proto) and any("WdConvGemm" in p or ADDRESSING.match(p.split()[-1].lstrip("*")) for p in proto[1])
 
 
 def test_every_entry_with_a_stride_row_count_or_class_offset_has_a_case_or_an_exemption():
-    decl = _declared()
+    from tests.abi_decl import declared
+    decl = {name: proto for h in HEADERS for name, proto in declared(h).items()}      # every wd_* function of the five headers
     assert len(decl) >= 70 and {"wd_conv_gemm", "wd_layernorm_rows", "wd_topk_candidates", "wd_group_rows"} <= set(decl)
     covered = {c.entry for c in O.CASES}
     assert not covered - set(decl), f"cases for entry points no header declares: {sorted(covered - set(decl))}"

@@ -66,13 +66,15 @@ def test_lists_and_select_rules():
 
 
 def test_header_entry_list_matches_the_binding_and_every_entry_has_an_extent_case():
+    from tests.abi_decl import declared
+    from tests.test_cpu_abi import check_header
     from wedetect_amd import build as WB
     from wedetect_amd import lib as L
     from wedetect_amd import sparse as SP
     hdr = open(os.path.join(ROOT, "include", "wedetect_hip_sparse.h")).read()
-    body = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    names = re.findall(r"^\s*(?:int|int32_t|int64_t)\s+(wd_\w+)\s*\(", body, flags=re.M)
-    assert sorted(names) == sorted(SP.EXPORTS) and len(set(names)) == len(names)
+    names = list(declared("wedetect_hip_sparse.h"))
+    assert sorted(names) == sorted(SP.EXPORTS)
+    check_header("wedetect_hip_sparse.h")                        # argtypes / restype against the prototypes
     assert "wedetect_hip_sparse.h" in WB.PUBLIC_HEADERS and "sparse.hip" in WB.SOURCES
     assert "sparse.hip" in WB.NO_SCRATCH and "sparse.hip" in WB.ASM_VMEM_SOURCES and "split_gemm_p8_kernel" in WB.NO_SCRATCH["split_gemm_p8.hip"]
     for name, val in (("WD_SPARSE_OK", 0), ("WD_SPARSE_OVERFLOW", 1), ("WD_SPARSE_NONFINITE", 2)):

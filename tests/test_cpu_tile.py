@@ -4,7 +4,6 @@ import ctypes
 import fnmatch
 import hashlib
 import os
-import re
 import sys
 
 import numpy as np
@@ -16,18 +15,13 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 from tests import tile_ref as R  # noqa: E402
+from tests.abi_decl import declared  # noqa: E402
 from wedetect_amd import tiling as G  # noqa: E402
 
-TILE_HEADER = os.path.join(ROOT, "include", "wedetect_hip_tile.h")
+TILE_HEADER = "wedetect_hip_tile.h"
 # sha256 of include/wedetect_hip.h at ABI 15 (tests/test_cpu_feed.py pins the same): the tile entry points live in a header of
 # their own, the frozen one does not move
 MAIN_HEADER_SHA256 = "2b62a824664907f02d66fef8abe43f4c50fa0703c00814e15a08129143937784"
-
-
-def _declared():
-    hdr = open(TILE_HEADER).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    return {m.group(1): m.group(2) for m in re.finditer(r"\b(wd_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", hdr)}
 
 
 # ------------------------------------------------------------------------------------------------------------------ plan
@@ -115,7 +109,7 @@ def test_overview_geometry_is_the_test_pipelines_own():
 def test_library_exports_the_tile_header_and_the_frozen_abi_is_untouched():
     from wedetect_amd import build as wb
     wb.build(verbose=False)
-    decl = set(_declared())
+    decl = set(declared(TILE_HEADER))
     assert {"wd_tile_abi_version", "wd_tile_sizeof_tile", "wd_tile_cut_u8", "wd_tile_merge", "wd_tile_merge_workspace_bytes"} == decl
     lib = ctypes.CDLL(wb.LIB)
     assert not [s for s in sorted(decl) if not hasattr(lib, s)]
@@ -144,7 +138,7 @@ def test_library_exports_the_tile_header_and_the_frozen_abi_is_untouched():
 def test_every_tile_entry_point_with_device_memory_has_an_extents_case():
     from tests.test_cpu_arena import EXEMPT_ALLOWED, _takes_memory
     from tests.test_gpu_tile_extents import CASES, EXEMPT
-    decl = _declared()
+    decl = declared(TILE_HEADER)
     covered = {c.entry for c in CASES}
     allowed = EXEMPT_ALLOWED + ("wd_tile_abi_version", "wd_tile_sizeof_*")
     for name in sorted(decl):

@@ -159,30 +159,17 @@ def test_script_says_why_it_refuses_top_names_without_best_class(capsys):
     assert "--top-names needs --best-class" in capsys.readouterr().err
 
 
-def _c_to_ctypes(decl: str):
-    import ctypes as C
-    out = []
-    for arg in [a.strip() for a in decl.split(",")]:
-        if "*" in arg:
-            out.append(C.POINTER(C.c_float) if re.match(r"const float\*\s*seg_", arg) else C.c_void_p)
-        else:
-            out.append({"int32_t": C.c_int32, "int64_t": C.c_int64, "float": C.c_float}[arg.split()[0]])
-    return out
-
-
 def test_header_prototypes_match_the_binding_and_every_entry_has_an_extent_case():
+    from tests.abi_decl import declared
+    from tests.test_cpu_abi import check_header
     from wedetect_amd import build as WB
     from wedetect_amd import lib as L
     from wedetect_amd import topn as TN
     hdr = open(os.path.join(ROOT, "include", "wedetect_hip_topn.h")).read()
-    body = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    protos = {m.group(1): m.group(2) for m in re.finditer(r"^\s*int\s+(wd_\w+)\s*\(([^)]*)\)\s*;", body, flags=re.M)}
-    assert sorted(protos) == sorted(TN.EXPORTS)
+    protos = declared("wedetect_hip_topn.h")
+    assert sorted(protos) == sorted(TN.EXPORTS) and all(ret == "int" for ret, _ in protos.values())
     assert "wedetect_hip_topn.h" in WB.PUBLIC_HEADERS and "topn.hip" in WB.SOURCES
-    for name, decl in protos.items():
-        if name == "wd_topn_abi_version":
-            continue
-        assert list(getattr(TN.LIB, name).argtypes) == _c_to_ctypes(" ".join(decl.split())), name
+    check_header("wedetect_hip_topn.h")                       # argtypes / restype against the prototypes
     assert re.search(r"#define\s+WD_TOPN_MAX\s+8\b", hdr) and TN.TOPN_MAX == 8
     assert TN.LIB.wd_topn_abi_version() == TN.TOPN_ABI_VERSION == 1
     assert L.LIB.wd_abi_version() == L.ABI_VERSION == 15       # the main ABI stays

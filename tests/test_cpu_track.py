@@ -12,17 +12,13 @@ import pytest
 import tests.track_hazards  # noqa: F401  (declares the wrappers of wedetect_amd/track.py to tests/hazards.py)
 from tests import track_cases as TC
 from tests import track_ref as R
+from tests.abi_decl import declared
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "wedetect_hip_track.h")
 f32 = np.float32
 NAMES = ["wd_track_abi_version", "wd_track_export", "wd_track_reset", "wd_track_state_bytes", "wd_track_step", "wd_track_workspace_bytes"]
 SIZE_QUERIES = ("wd_track_abi_version", "wd_track_state_bytes", "wd_track_workspace_bytes")
-
-
-def _declared():
-    hdr = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    return {m.group(1): m.group(2) for m in re.finditer(r"\b(wd_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", hdr)}
 
 
 # ------------------------------------------------------------------------------------------------------------ reference
@@ -146,10 +142,11 @@ def test_crossing_objects_keep_their_ids_by_appearance_and_swap_them_without():
 
 # ------------------------------------------------------------------------------------------------- header, library, build
 def test_library_exports_the_header_and_the_frozen_abi_is_untouched():
+    from tests.test_cpu_abi import check_header
     from tests.test_cpu_tile import MAIN_HEADER_SHA256
     from wedetect_amd import lib as L
     from wedetect_amd import track as T
-    decl = _declared()
+    decl = declared("wedetect_hip_track.h")
     assert sorted(decl) == sorted(T.EXPORTS) == NAMES
     for name in decl:
         assert hasattr(L.LIB, name)
@@ -162,11 +159,10 @@ def test_library_exports_the_header_and_the_frozen_abi_is_untouched():
         assert re.search(rf"#define\s+{macro}\s+{val}\b", hdr), macro
     assert (T.STATUS_FULL, T.STATUS_BAD_COUNT) == (R.STATUS_FULL, R.STATUS_BAD_COUNT)
     conv = {"int32_t": ctypes.c_int32, "float": ctypes.c_float}
-    for name, params in decl.items():
+    check_header("wedetect_hip_track.h")                                      # argtypes / restype against the prototypes
+    for name in decl:
         if name == "wd_track_abi_version":
             continue
-        want = [ctypes.c_void_p if "*" in p else conv[p.split()[0]] for p in (" ".join(q.split()) for q in params.split(","))]
-        assert list(getattr(T.LIB, name).argtypes) == want, name
         if name in SIZE_QUERIES:
             assert getattr(T.LIB, name).restype is ctypes.c_int64 and re.search(rf"int64_t\s+{name}\(", hdr)
             continue
@@ -256,7 +252,7 @@ def test_argument_refusals_before_any_launch():
 def test_every_track_entry_point_with_device_memory_has_an_extents_case():
     from tests.test_cpu_arena import _takes_memory
     from tests.test_gpu_track_extents import CASES
-    decl = _declared()
+    decl = declared("wedetect_hip_track.h")
     covered = {c.entry for c in CASES}
     for name, params in sorted(decl.items()):
         if name in SIZE_QUERIES:

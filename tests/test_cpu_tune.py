@@ -12,16 +12,12 @@ import pytest
 
 import tests.tune_hazards  # noqa: F401  (declares the wrappers of wedetect_amd/tune.py to tests/hazards.py)
 from tests import tune_ref as R
+from tests.abi_decl import declared
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "wedetect_hip_tune.h")
 f32, f64 = np.float32, np.float64
 NAMES = ["wd_tune_abi_version", "wd_tune_grad", "wd_tune_plan", "wd_tune_targets", "wd_tune_update"]
-
-
-def _declared():
-    hdr = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    return {m.group(1): m.group(2) for m in re.finditer(r"\b(wd_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", hdr)}
 
 
 def _chunks(K, dim=R.DIM):
@@ -132,10 +128,11 @@ def test_plan_covers_every_row_once_and_matches_the_library():
 
 # ------------------------------------------------------------------------------------------------- header, library, build
 def test_library_exports_the_header_and_the_frozen_abi_is_untouched():
+    from tests.test_cpu_abi import check_header
     from tests.test_cpu_tile import MAIN_HEADER_SHA256
     from wedetect_amd import lib as L
     from wedetect_amd import tune as TN
-    decl = _declared()
+    decl = declared("wedetect_hip_tune.h")
     assert sorted(decl) == sorted(TN.EXPORTS) == NAMES
     for name in decl:
         assert hasattr(L.LIB, name)
@@ -147,14 +144,10 @@ def test_library_exports_the_header_and_the_frozen_abi_is_untouched():
                            ("WD_TUNE_MAX_SPLIT", 256, TN.MAX_SPLIT)):
         assert re.search(rf"#define\s+{macro}\s+{val}\b", hdr) and py == val, macro
     assert (R.DIM, R.CLASS_BLOCK, R.ROW_TILE, R.MAX_SPLIT) == (TN.DIM, TN.CLASS_BLOCK, TN.ROW_TILE, TN.MAX_SPLIT)
-    conv = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float}
-    for name, params in decl.items():
-        if name == "wd_tune_abi_version":
-            continue
-        want = [ctypes.c_void_p if "*" in p else conv[p.split()[0]] for p in (" ".join(q.split()) for q in params.split(","))]
-        assert list(getattr(TN.LIB, name).argtypes) == want, name
-        if name == "wd_tune_plan":
-            assert TN.LIB.wd_tune_plan.restype is ctypes.c_int32
+    check_header("wedetect_hip_tune.h")                                        # argtypes / restype against the prototypes
+    assert decl["wd_tune_plan"][0] == "int32_t" and TN.LIB.wd_tune_plan.restype is ctypes.c_int32
+    for name in decl:
+        if name in ("wd_tune_abi_version", "wd_tune_plan"):
             continue
         doc = hdr[: hdr.index(f"int {name}(")].rsplit("/* ----", 1)[1]
         assert "Extents:" in doc and "WD_ERR_BAD_ARG:" in doc, name
@@ -212,7 +205,7 @@ def test_argument_refusals_before_any_launch():
 def test_every_tune_entry_point_with_device_memory_has_an_extents_case():
     from tests.test_cpu_arena import _takes_memory
     from tests.test_gpu_tune_extents import CASES
-    decl = _declared()
+    decl = declared("wedetect_hip_tune.h")
     covered = {c.entry for c in CASES}
     for name, params in sorted(decl.items()):
         if name in ("wd_tune_abi_version", "wd_tune_plan"):

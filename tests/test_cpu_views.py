@@ -5,7 +5,6 @@ import ctypes
 import fnmatch
 import hashlib
 import os
-import re
 import sys
 
 import numpy as np
@@ -17,16 +16,11 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 from tests import views_ref as R  # noqa: E402
+from tests.abi_decl import declared  # noqa: E402
 
-VIEWS_HEADER = os.path.join(ROOT, "include", "wedetect_hip_views.h")
+VIEWS_HEADER = "wedetect_hip_views.h"
 # sha256 of include/wedetect_hip.h at ABI 15 (tests/test_cpu_feed.py and tests/test_cpu_tile.py pin the same)
 MAIN_HEADER_SHA256 = "2b62a824664907f02d66fef8abe43f4c50fa0703c00814e15a08129143937784"
-
-
-def _declared():
-    hdr = open(VIEWS_HEADER).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    return {m.group(1): m.group(2) for m in re.finditer(r"\b(wd_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", hdr)}
 
 
 def _entry():
@@ -268,7 +262,7 @@ def test_test_py_flags(capsys):
 def test_library_exports_the_views_header_and_the_frozen_abi_is_untouched():
     from wedetect_amd import build as wb
     wb.build(verbose=False)
-    decl = set(_declared())
+    decl = set(declared(VIEWS_HEADER))
     assert {"wd_views_abi_version", "wd_flip_u8", "wd_views_merge", "wd_views_merge_workspace_bytes"} == decl
     lib = ctypes.CDLL(wb.LIB)
     assert not [s for s in sorted(decl) if not hasattr(lib, s)]
@@ -308,7 +302,7 @@ def test_library_exports_the_views_header_and_the_frozen_abi_is_untouched():
 def test_every_views_entry_point_with_device_memory_has_an_extents_case():
     from tests.test_cpu_arena import EXEMPT_ALLOWED, _takes_memory
     from tests.test_gpu_views_extents import CASES, EXEMPT
-    decl = _declared()
+    decl = declared(VIEWS_HEADER)
     covered = {c.entry for c in CASES}
     allowed = EXEMPT_ALLOWED + ("wd_views_abi_version",)
     for name in sorted(decl):

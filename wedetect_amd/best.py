@@ -4,42 +4,23 @@ of csrc/split_gemm_p8.hip, the labeled form of the NMS kernel in csrc/postproces
 feed.py, tile.py, views.py and fold.py: a version and an export list of its own, the main ABI stays as it is."""
 from __future__ import annotations
 
-import ctypes as C
-
 from . import lib as L
+from .lib import f32, fp, i32, i64, vp
 
 BEST_ABI_VERSION = 1
 NMS_MMCV_AGNOSTIC = 3            # WD_NMS_MMCV_AGNOSTIC: mmcv.ops.batched_nms(..., class_agnostic=True)
 FUSED_CHUNK = 1 << 20            # classes per wd_best_similarity_split launch (32-bit DMA offsets: n_cls * 768 * 4 < 2^32)
 ROWS_CHUNK = 4096                # classes per materialised block on the other paths
 
-EXPORTS = ("wd_best_abi_version", "wd_best_similarity_split", "wd_best_rows", "wd_best_unpack", "wd_nms_gather_labeled")
-
-
-def _bind():
-    lib = L.LIB
-    for name in EXPORTS:
-        if not hasattr(lib, name):
-            raise L.WedetectHipMissing(f"{L.LIB_PATH} does not export {name}; rebuild (python -m wedetect_amd.build)")
-    vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
-    fp = C.POINTER(C.c_float)
-    lib.wd_best_abi_version.restype = C.c_int
-    lib.wd_best_similarity_split.argtypes = [vp, i64, vp, f32, i32, i32, i32, i32, i32, fp, fp, vp, i32, vp, vp]
-    lib.wd_best_rows.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp]
-    lib.wd_best_unpack.argtypes = [vp, i64, vp, vp, vp]
-    lib.wd_nms_gather_labeled.argtypes = [vp, vp, vp, i32, vp, i32, vp, i32, vp, f32, i32, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp,
-                                          i32, vp, i64, vp]
-    if lib.wd_best_abi_version() != BEST_ABI_VERSION:
-        raise L.WedetectHipMissing(f"best ABI mismatch: library {lib.wd_best_abi_version()} vs binding {BEST_ABI_VERSION}; rebuild")
-    return lib
-
-
-LIB = _bind()
-
-
-def _ptr(t) -> int:
-    """A tensor's address, an address given as an int, or 0."""
-    return 0 if t is None else (int(t) if isinstance(t, int) else t.data_ptr())
+SIGNATURES = {
+    "wd_best_abi_version": (None, []),
+    "wd_best_similarity_split": (None, [vp, i64, vp, f32, i32, i32, i32, i32, i32, fp, fp, vp, i32, vp, vp]),
+    "wd_best_rows": (None, [vp, i32, i32, i32, i32, i32, vp, vp, vp]),
+    "wd_best_unpack": (None, [vp, i64, vp, vp, vp]),
+    "wd_nms_gather_labeled": (None, [vp, vp, vp, i32, vp, i32, vp, i32, vp, f32, i32, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, i64, vp]),
+}
+EXPORTS = tuple(SIGNATURES)
+LIB = L.bind("best", BEST_ABI_VERSION, SIGNATURES)
 
 
 def pack_key(score_bits, cls):
@@ -61,32 +42,28 @@ def best_similarity_split(e_split, rows, t_split, unscale, n_cls, dim, key, cls_
     """``wd_best_similarity_split`` on the current stream; operands as :func:`lib.similarity_split`.  ``t_row``: the row of
     the split bank ``t_split`` at which this launch's chunk of ``n_cls`` rows begins (a multiple of eight unless the chunk ends
     the bank), ``cls_offset`` the class index of that row.  ``key``: int64 [rows]."""
-    sr, e0, e1 = (int(seg[0]), int(seg[1]), int(seg[2])) if seg is not None else (0, 0, 0)
-    sc = (C.c_float * 3)(*[float(v) for v in (seg[3] if seg is not None else (1, 1, 1))])
-    sb = (C.c_float * 3)(*[float(v) for v in (seg[4] if seg is not None else (0, 0, 0))])
-    t_ptr = _ptr(t_split) + int(t_row) * ((int(dim) + 15) // 16 * 16) * 4
-    L.check(LIB.wd_best_similarity_split(_ptr(e_split), int(rows), t_ptr, float(unscale), int(n_cls), int(dim), sr, e0, e1,
-                                         sc, sb, _ptr(range_flag), int(cls_offset), _ptr(key), L.stream_ptr()),
+    sr, e0, e1, sc, sb = L.seg_args(seg)
+    L.check(LIB.wd_best_similarity_split(L.ptr(e_split), int(rows), L.bank_row_ptr(t_split, t_row, dim), float(unscale), int(n_cls),
+                                         int(dim), sr, e0, e1, sc, sb, L.ptr(range_flag), int(cls_offset), L.ptr(key), L.stream_ptr()),
             "wd_best_similarity_split")
 
 
 def best_rows(scores, n_img, rows_per_img, n_cls, ld, key, cls_offset=0, count=None) -> None:
     """``wd_best_rows`` on the current stream: merge the best column of every row of a [n_img * rows_per_img, ld] block."""
-    L.check(LIB.wd_best_rows(_ptr(scores), int(n_img), int(rows_per_img), int(n_cls), int(ld), int(cls_offset), _ptr(count), _ptr(key),
+    L.check(LIB.wd_best_rows(L.ptr(scores), int(n_img), int(rows_per_img), int(n_cls), int(ld), int(cls_offset), L.ptr(count), L.ptr(key),
                              L.stream_ptr()), "wd_best_rows")
 
 
 def best_unpack(key, rows, scores_out, labels_out) -> None:
-    L.check(LIB.wd_best_unpack(_ptr(key), int(rows), _ptr(scores_out), _ptr(labels_out), L.stream_ptr()), "wd_best_unpack")
+    L.check(LIB.wd_best_unpack(L.ptr(key), int(rows), L.ptr(scores_out), L.ptr(labels_out), L.stream_ptr()), "wd_best_unpack")
 
 
 def nms_gather_labeled(cand_idx, cand_score, cand_count, cand_stride, boxes, n_anchor, anchor_labels, n_label, meta, iou_thr, max_out,
                        embed, embed_dim, out_boxes, out_scores, out_labels, out_anchors, out_count, out_embed, batch,
                        nms_mode: int = L.NMS_VANILLA, mode_param: int = 0, workspace=None) -> None:
     """``wd_nms_gather_labeled`` on the current stream; ``iou_thr`` already rounded (:func:`lib.nms_threshold`)."""
-    ws_bytes = 0 if workspace is None else workspace.numel() * workspace.element_size()
-    L.check(LIB.wd_nms_gather_labeled(_ptr(cand_idx), _ptr(cand_score), _ptr(cand_count), int(cand_stride), _ptr(boxes), int(n_anchor),
-                                      _ptr(anchor_labels), int(n_label), _ptr(meta), float(iou_thr), int(max_out), int(nms_mode),
-                                      int(mode_param), _ptr(embed), int(embed_dim), _ptr(out_boxes), _ptr(out_scores), _ptr(out_labels),
-                                      _ptr(out_anchors), _ptr(out_count), _ptr(out_embed), int(batch), _ptr(workspace), ws_bytes,
+    L.check(LIB.wd_nms_gather_labeled(L.ptr(cand_idx), L.ptr(cand_score), L.ptr(cand_count), int(cand_stride), L.ptr(boxes), int(n_anchor),
+                                      L.ptr(anchor_labels), int(n_label), L.ptr(meta), float(iou_thr), int(max_out), int(nms_mode),
+                                      int(mode_param), L.ptr(embed), int(embed_dim), L.ptr(out_boxes), L.ptr(out_scores), L.ptr(out_labels),
+                                      L.ptr(out_anchors), L.ptr(out_count), L.ptr(out_embed), int(batch), L.ptr(workspace), L.nbytes(workspace),
                                       L.stream_ptr()), "wd_nms_gather_labeled")

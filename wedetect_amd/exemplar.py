@@ -4,32 +4,20 @@ class (``wd_exemplar_pool``).  Between the two the kept-rows route of fold.py co
 the three embedding GEMMs).  A version and an export list of its own, like topn.py: the main ABI stays as it is."""
 from __future__ import annotations
 
-import ctypes as C
-
 from . import lib as L
+from .lib import f32, i32, vp
 
 EXEMPLAR_ABI_VERSION = 1
 MAX_M = 8                        # WD_EXEMPLAR_MAX_M
 MAX_EX = 64                      # WD_EXEMPLAR_MAX_EX
 
-EXPORTS = ("wd_exemplar_abi_version", "wd_exemplar_assign", "wd_exemplar_pool")
-
-
-def _bind():
-    lib = L.LIB
-    for name in EXPORTS:
-        if not hasattr(lib, name):
-            raise L.WedetectHipMissing(f"{L.LIB_PATH} does not export {name}; rebuild (python -m wedetect_amd.build)")
-    vp, i32, f32 = C.c_void_p, C.c_int32, C.c_float
-    lib.wd_exemplar_abi_version.restype = C.c_int
-    lib.wd_exemplar_assign.argtypes = [vp, i32, vp, vp, vp, i32, i32, i32, f32, vp, vp, vp, vp]
-    lib.wd_exemplar_pool.argtypes = [vp, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp]
-    if lib.wd_exemplar_abi_version() != EXEMPLAR_ABI_VERSION:
-        raise L.WedetectHipMissing(f"exemplar ABI mismatch: library {lib.wd_exemplar_abi_version()} vs binding {EXEMPLAR_ABI_VERSION}; rebuild")
-    return lib
-
-
-LIB = _bind()
+SIGNATURES = {
+    "wd_exemplar_abi_version": (None, []),
+    "wd_exemplar_assign": (None, [vp, i32, vp, vp, vp, i32, i32, i32, f32, vp, vp, vp, vp]),
+    "wd_exemplar_pool": (None, [vp, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp]),
+}
+EXPORTS = tuple(SIGNATURES)
+LIB = L.bind("exemplar", EXEMPLAR_ABI_VERSION, SIGNATURES)
 
 
 def check_m(m) -> int:
@@ -51,8 +39,8 @@ def exemplar_assign(boxes, n_anchor: int, ex_boxes, ex_count, meta, max_ex: int,
     """``wd_exemplar_assign`` on the current stream: ``boxes`` fp32 [batch, n_anchor, 4] (network pixels), ``ex_boxes`` fp32
     [batch, max_ex, 4] (original-image pixels), ``ex_count`` int32 [batch], ``meta`` fp32 [batch, 8]; writes ``sel_anchors`` int32
     / ``sel_iou`` fp32 [batch, max_ex * m] and ``sel_count`` int32 [batch], whole."""
-    L.check(LIB.wd_exemplar_assign(L._p(boxes), int(n_anchor), L._p(ex_boxes), L._p(ex_count), L._p(meta), int(max_ex), int(batch),
-                                   int(m), float(min_iou), L._p(sel_anchors), L._p(sel_iou), L._p(sel_count), L.stream_ptr()),
+    L.check(LIB.wd_exemplar_assign(L.ptr(boxes), int(n_anchor), L.ptr(ex_boxes), L.ptr(ex_count), L.ptr(meta), int(max_ex), int(batch),
+                                   int(m), float(min_iou), L.ptr(sel_anchors), L.ptr(sel_iou), L.ptr(sel_count), L.stream_ptr()),
             "wd_exemplar_assign")
 
 
@@ -61,6 +49,6 @@ def exemplar_pool(level_embed, dim: int, off1: int, off2: int, sel_anchors, sel_
     """``wd_exemplar_pool`` on the current stream: ``level_embed`` fp32 [3, n_slot, dim] (the three embedding GEMMs' outputs on the
     gathered rows), ``cls_off`` int32 [n_cls + 1] / ``cls_slot`` int32 [cls_off[-1]] the classes' slot lists; writes ``bank`` fp32
     [n_cls, dim] and ``support`` int32 [n_cls], whole."""
-    L.check(LIB.wd_exemplar_pool(L._p(level_embed), int(dim), int(off1), int(off2), L._p(sel_anchors), L._p(sel_iou), int(n_slot),
-                                 L._p(cls_off), L._p(cls_slot), int(n_cls), L._p(bank), L._p(support), L.stream_ptr()),
+    L.check(LIB.wd_exemplar_pool(L.ptr(level_embed), int(dim), int(off1), int(off2), L.ptr(sel_anchors), L.ptr(sel_iou), int(n_slot),
+                                 L.ptr(cls_off), L.ptr(cls_slot), int(n_cls), L.ptr(bank), L.ptr(support), L.stream_ptr()),
             "wd_exemplar_pool")

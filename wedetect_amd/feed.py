@@ -17,12 +17,19 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import lib as L
+from .lib import i32, i64, vp
 
 FEED_ABI_VERSION = 1
 FEED_PILLOW = 4
 ALIGN = 256                      # images in the pixel arena, the table arena in the control block, tmp ranges
 
-EXPORTS = ("wd_feed_abi_version", "wd_feed_sizeof_image", "wd_feed_tmp_bytes", "wd_feed_batch_u8")
+SIGNATURES = {
+    "wd_feed_abi_version": (None, []),
+    "wd_feed_sizeof_image": (i32, []),
+    "wd_feed_tmp_bytes": (i64, [i32, i32]),
+    "wd_feed_batch_u8": (None, [vp, i64, vp, vp, i32, vp, i64, vp, i64, vp, i32, i32, vp]),
+}
+EXPORTS = tuple(SIGNATURES)
 
 
 class FeedImage(C.Structure):
@@ -41,25 +48,9 @@ IMAGE_DTYPE = np.dtype([(n, {C.c_int64: "<i8", C.c_int32: "<i4", C.c_float: "<f4
 TABLE_FIELDS = ("xa", "xidx", "xw", "ya", "yidx", "yw")
 
 
-def _bind():
-    lib = L.LIB
-    for name in EXPORTS:
-        if not hasattr(lib, name):
-            raise L.WedetectHipMissing(f"{L.LIB_PATH} does not export {name}; rebuild (python -m wedetect_amd.build)")
-    vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
-    lib.wd_feed_abi_version.restype = C.c_int
-    lib.wd_feed_sizeof_image.restype = i32
-    lib.wd_feed_tmp_bytes.restype = i64
-    lib.wd_feed_tmp_bytes.argtypes = [i32, i32]
-    lib.wd_feed_batch_u8.argtypes = [vp, i64, vp, vp, i32, vp, i64, vp, i64, vp, i32, i32, vp]
-    if lib.wd_feed_abi_version() != FEED_ABI_VERSION:
-        raise L.WedetectHipMissing(f"feed ABI mismatch: library {lib.wd_feed_abi_version()} vs binding {FEED_ABI_VERSION}; rebuild")
-    if not (lib.wd_feed_sizeof_image() == C.sizeof(FeedImage) == IMAGE_DTYPE.itemsize):
-        raise L.WedetectHipMissing("struct WdFeedImage layout differs between the library and feed.FeedImage; rebuild")
-    return lib
-
-
-LIB = _bind()
+LIB = L.bind("feed", FEED_ABI_VERSION, SIGNATURES)
+if not (LIB.wd_feed_sizeof_image() == C.sizeof(FeedImage) == IMAGE_DTYPE.itemsize):
+    raise L.WedetectHipMissing("struct WdFeedImage layout differs between the library and feed.FeedImage; rebuild")
 
 
 def _up(n: int, a: int = ALIGN) -> int:
@@ -188,7 +179,7 @@ def feed_batch_u8(src, images_dev_ptr: int, images_host: np.ndarray, tables_dev_
     if images_host.dtype != IMAGE_DTYPE or images_host.size != b or not images_host.flags.c_contiguous:
         raise L.WedetectHipError(f"feed_batch_u8: {b} descriptors expected")
     L.check(LIB.wd_feed_batch_u8(src.data_ptr(), src.numel(), images_dev_ptr, images_host.ctypes.data, b,
-                                 tables_dev_ptr if table_elems else 0, int(table_elems), L._p(tmp), 0 if tmp is None else tmp.numel(),
+                                 tables_dev_ptr if table_elems else 0, int(table_elems), L.ptr(tmp), 0 if tmp is None else tmp.numel(),
                                  dst.data_ptr(), int(dst.shape[1]), int(dst.shape[2]), L.stream_ptr()), "wd_feed_batch_u8")
     return launches(images_host)
 

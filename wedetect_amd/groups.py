@@ -4,39 +4,26 @@ ctypes binding of the two entry points.  A version and an export list of its own
 ABI stays as it is."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
 
 from . import lib as L
-from .best import _ptr
+from .lib import f32, fp, i32, i64, vp
 
 GROUPS_ABI_VERSION = 1
 BIN = 32                         # WD_GROUP_BIN: bank rows per bin; no class straddles one
 FUSED_CHUNK = 1 << 20            # bank rows per wd_group_similarity_split launch (32-bit DMA offsets); a multiple of BIN
 ROWS_CHUNK = 4096                # bank rows per materialised block on the other paths; a multiple of BIN
 
-EXPORTS = ("wd_groups_abi_version", "wd_group_similarity_split", "wd_group_rows")
-
-
-def _bind():
-    lib = L.LIB
-    for name in EXPORTS:
-        if not hasattr(lib, name):
-            raise L.WedetectHipMissing(f"{L.LIB_PATH} does not export {name}; rebuild (python -m wedetect_amd.build)")
-    vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
-    fp = C.POINTER(C.c_float)
-    lib.wd_groups_abi_version.restype = C.c_int
-    lib.wd_group_similarity_split.argtypes = [vp, i64, vp, f32, i32, i32, i32, i32, i32, fp, fp, vp, vp, vp, i32, vp, i32, i32, vp]
-    lib.wd_group_rows.argtypes = [vp, i64, i32, i32, vp, vp, i32, vp, i32, i32, vp]
-    if lib.wd_groups_abi_version() != GROUPS_ABI_VERSION:
-        raise L.WedetectHipMissing(f"groups ABI mismatch: library {lib.wd_groups_abi_version()} vs binding {GROUPS_ABI_VERSION}; rebuild")
-    return lib
-
-
-LIB = _bind()
+SIGNATURES = {
+    "wd_groups_abi_version": (None, []),
+    "wd_group_similarity_split": (None, [vp, i64, vp, f32, i32, i32, i32, i32, i32, fp, fp, vp, vp, vp, i32, vp, i32, i32, vp]),
+    "wd_group_rows": (None, [vp, i64, i32, i32, vp, vp, i32, vp, i32, i32, vp]),
+}
+EXPORTS = tuple(SIGNATURES)
+LIB = L.bind("groups", GROUPS_ABI_VERSION, SIGNATURES)
 
 
 class PromptGroups:
@@ -144,17 +131,14 @@ def group_similarity_split(e_split, rows, t_split, unscale, n_cls, dim, group_of
     """``wd_group_similarity_split`` on the current stream; operands as :func:`best.best_similarity_split`.  ``group_of`` /
     ``bin_first``: the WHOLE device tables of the plan; ``cls_offset`` the bank row at which this launch's ``n_cls`` rows begin
     (both multiples of 32), ``t_row`` that row's position in ``t_split``.  ``out`` fp32 rows of stride ``ldo``."""
-    sr, e0, e1 = (int(seg[0]), int(seg[1]), int(seg[2])) if seg is not None else (0, 0, 0)
-    sc = (C.c_float * 3)(*[float(v) for v in (seg[3] if seg is not None else (1, 1, 1))])
-    sb = (C.c_float * 3)(*[float(v) for v in (seg[4] if seg is not None else (0, 0, 0))])
-    t_ptr = _ptr(t_split) + int(t_row) * ((int(dim) + 15) // 16 * 16) * 4
-    L.check(LIB.wd_group_similarity_split(_ptr(e_split), int(rows), t_ptr, float(unscale), int(n_cls), int(dim), sr, e0, e1, sc, sb,
-                                          _ptr(range_flag), _ptr(group_of), _ptr(bin_first), int(cls_offset), _ptr(out), int(ldo),
-                                          int(n_groups), L.stream_ptr()), "wd_group_similarity_split")
+    sr, e0, e1, sc, sb = L.seg_args(seg)
+    L.check(LIB.wd_group_similarity_split(L.ptr(e_split), int(rows), L.bank_row_ptr(t_split, t_row, dim), float(unscale), int(n_cls),
+                                          int(dim), sr, e0, e1, sc, sb, L.ptr(range_flag), L.ptr(group_of), L.ptr(bin_first),
+                                          int(cls_offset), L.ptr(out), int(ldo), int(n_groups), L.stream_ptr()), "wd_group_similarity_split")
 
 
 def group_rows(block, rows, n_cls, ld, group_of, bin_first, cls_offset, out, ldo, n_groups) -> None:
     """``wd_group_rows`` on the current stream: the class maxima of a materialised [rows, ld] block of scores of bank rows
     [cls_offset, cls_offset + n_cls)."""
-    L.check(LIB.wd_group_rows(_ptr(block), int(rows), int(n_cls), int(ld), _ptr(group_of), _ptr(bin_first), int(cls_offset), _ptr(out),
+    L.check(LIB.wd_group_rows(L.ptr(block), int(rows), int(n_cls), int(ld), L.ptr(group_of), L.ptr(bin_first), int(cls_offset), L.ptr(out),
                               int(ldo), int(n_groups), L.stream_ptr()), "wd_group_rows")

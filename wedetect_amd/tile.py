@@ -9,13 +9,21 @@ import ctypes as C
 import numpy as np
 
 from . import lib as L
+from .lib import f32, i32, i64, vp
 from .tiling import TILE_DTYPE, TILE_FIELDS
 
 TILE_ABI_VERSION = 1
 MERGE_MAX_ROWS = 32768           # n_tile * max_in of one wd_tile_merge call
 MERGE_MAX_OUT = 1024
 
-EXPORTS = ("wd_tile_abi_version", "wd_tile_sizeof_tile", "wd_tile_cut_u8", "wd_tile_merge_workspace_bytes", "wd_tile_merge")
+SIGNATURES = {
+    "wd_tile_abi_version": (None, []),
+    "wd_tile_sizeof_tile": (i32, []),
+    "wd_tile_cut_u8": (None, [vp, i32, i32, i64, vp, vp, i32, i32, i32, i32, i32, vp, vp]),
+    "wd_tile_merge_workspace_bytes": (i64, [i32, i32]),
+    "wd_tile_merge": (None, [vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp]),
+}
+EXPORTS = tuple(SIGNATURES)
 
 
 class Tile(C.Structure):
@@ -23,26 +31,9 @@ class Tile(C.Structure):
     _fields_ = [(n, C.c_int32) for n in TILE_FIELDS]
 
 
-def _bind():
-    lib = L.LIB
-    for name in EXPORTS:
-        if not hasattr(lib, name):
-            raise L.WedetectHipMissing(f"{L.LIB_PATH} does not export {name}; rebuild (python -m wedetect_amd.build)")
-    vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
-    lib.wd_tile_abi_version.restype = C.c_int
-    lib.wd_tile_sizeof_tile.restype = i32
-    lib.wd_tile_cut_u8.argtypes = [vp, i32, i32, i64, vp, vp, i32, i32, i32, i32, i32, vp, vp]
-    lib.wd_tile_merge_workspace_bytes.restype = i64
-    lib.wd_tile_merge_workspace_bytes.argtypes = [i32, i32]
-    lib.wd_tile_merge.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp]
-    if lib.wd_tile_abi_version() != TILE_ABI_VERSION:
-        raise L.WedetectHipMissing(f"tile ABI mismatch: library {lib.wd_tile_abi_version()} vs binding {TILE_ABI_VERSION}; rebuild")
-    if not (lib.wd_tile_sizeof_tile() == C.sizeof(Tile) == TILE_DTYPE.itemsize == 32):
-        raise L.WedetectHipMissing("struct WdTile layout differs between the library and tile.Tile; rebuild")
-    return lib
-
-
-LIB = _bind()
+LIB = L.bind("tile", TILE_ABI_VERSION, SIGNATURES)
+if not (LIB.wd_tile_sizeof_tile() == C.sizeof(Tile) == TILE_DTYPE.itemsize == 32):
+    raise L.WedetectHipMissing("struct WdTile layout differs between the library and tile.Tile; rebuild")
 
 
 def merge_workspace_bytes(n_tile: int, max_in: int) -> int:
@@ -77,5 +68,4 @@ def tile_merge(boxes, scores, labels, counts, plan_dev_ptr: int, n_tile: int, ma
     L.check(LIB.wd_tile_merge(boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(), counts.data_ptr(), plan_dev_ptr, int(n_tile),
                               int(max_in), int(n_cls), float(edge_margin), L.nms_threshold(iou_thr, L.NMS_MMCV), int(split_thr),
                               int(max_out), out_boxes.data_ptr(), out_scores.data_ptr(), out_labels.data_ptr(), out_src.data_ptr(),
-                              out_count.data_ptr(), workspace.data_ptr(), workspace.numel() * workspace.element_size(),
-                              L.stream_ptr()), "wd_tile_merge")
+                              out_count.data_ptr(), workspace.data_ptr(), L.nbytes(workspace), L.stream_ptr()), "wd_tile_merge")

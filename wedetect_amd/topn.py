@@ -5,37 +5,24 @@ cascade of atomic maxima, so a bank may be scored in DISJOINT chunks in any orde
 best.py and sparse.py: the main ABI stays as it is."""
 from __future__ import annotations
 
-import ctypes as C
-
 from . import lib as L
-from .best import _ptr, pack_key, unpack_key      # the key is the best-class key
+from .best import pack_key, unpack_key            # the key is the best-class key
+from .lib import f32, fp, i32, i64, vp
 
 TOPN_ABI_VERSION = 1
 TOPN_MAX = 8                     # WD_TOPN_MAX
 FUSED_CHUNK = 1 << 20            # classes per wd_topn_similarity_split launch (32-bit DMA offsets: n_cls * 768 * 4 < 2^32)
 ROWS_CHUNK = 4096                # classes per materialised block on the other paths
 
-EXPORTS = ("wd_topn_abi_version", "wd_topn_similarity_split", "wd_topn_rows", "wd_topn_unpack", "wd_topn_kept")
-
-
-def _bind():
-    lib = L.LIB
-    for name in EXPORTS:
-        if not hasattr(lib, name):
-            raise L.WedetectHipMissing(f"{L.LIB_PATH} does not export {name}; rebuild (python -m wedetect_amd.build)")
-    vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
-    fp = C.POINTER(C.c_float)
-    lib.wd_topn_abi_version.restype = C.c_int
-    lib.wd_topn_similarity_split.argtypes = [vp, i64, vp, f32, i32, i32, i32, i32, i32, fp, fp, vp, vp, vp, i32, i32, vp, vp]
-    lib.wd_topn_rows.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp]
-    lib.wd_topn_unpack.argtypes = [vp, i64, i32, i32, vp, vp, vp]
-    lib.wd_topn_kept.argtypes = [vp, i32, i32, vp, vp, i32, i32, vp, vp, vp]
-    if lib.wd_topn_abi_version() != TOPN_ABI_VERSION:
-        raise L.WedetectHipMissing(f"topn ABI mismatch: library {lib.wd_topn_abi_version()} vs binding {TOPN_ABI_VERSION}; rebuild")
-    return lib
-
-
-LIB = _bind()
+SIGNATURES = {
+    "wd_topn_abi_version": (None, []),
+    "wd_topn_similarity_split": (None, [vp, i64, vp, f32, i32, i32, i32, i32, i32, fp, fp, vp, vp, vp, i32, i32, vp, vp]),
+    "wd_topn_rows": (None, [vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp]),
+    "wd_topn_unpack": (None, [vp, i64, i32, i32, vp, vp, vp]),
+    "wd_topn_kept": (None, [vp, i32, i32, vp, vp, i32, i32, vp, vp, vp]),
+}
+EXPORTS = tuple(SIGNATURES)
+LIB = L.bind("topn", TOPN_ABI_VERSION, SIGNATURES)
 
 
 def check_n_top(n_top, lo: int = 1) -> int:
@@ -62,27 +49,24 @@ def topn_similarity_split(e_split, rows, t_split, unscale, n_cls, dim, n_top, ke
     """``wd_topn_similarity_split`` on the current stream; operands as :func:`best.best_similarity_split`.  ``key``: int64
     [rows, n_top], cleared by the caller before the first producer of a step.  ``row_scale`` / ``row_bias`` fp32 [rows]: the
     per-region affine, exclusive with ``seg``."""
-    sr, e0, e1 = (int(seg[0]), int(seg[1]), int(seg[2])) if seg is not None else (0, 0, 0)
-    sc = (C.c_float * 3)(*[float(v) for v in (seg[3] if seg is not None else (1, 1, 1))])
-    sb = (C.c_float * 3)(*[float(v) for v in (seg[4] if seg is not None else (0, 0, 0))])
-    t_ptr = _ptr(t_split) + int(t_row) * ((int(dim) + 15) // 16 * 16) * 4
-    L.check(LIB.wd_topn_similarity_split(_ptr(e_split), int(rows), t_ptr, float(unscale), int(n_cls), int(dim), sr, e0, e1, sc, sb,
-                                         _ptr(row_scale), _ptr(row_bias), _ptr(range_flag), int(cls_offset), int(n_top), _ptr(key),
-                                         L.stream_ptr()), "wd_topn_similarity_split")
+    sr, e0, e1, sc, sb = L.seg_args(seg)
+    L.check(LIB.wd_topn_similarity_split(L.ptr(e_split), int(rows), L.bank_row_ptr(t_split, t_row, dim), float(unscale), int(n_cls),
+                                         int(dim), sr, e0, e1, sc, sb, L.ptr(row_scale), L.ptr(row_bias), L.ptr(range_flag),
+                                         int(cls_offset), int(n_top), L.ptr(key), L.stream_ptr()), "wd_topn_similarity_split")
 
 
 def topn_rows(block, n_img, rows_per_img, n_cls, ld, n_top, key, cls_offset=0, count=None, row_scale=None, row_bias=None) -> None:
     """``wd_topn_rows`` on the current stream: merge the ``n_top`` best columns of every row of a [n_img * rows_per_img, ld] block
     (scores; raw logits where the row affine is given)."""
-    L.check(LIB.wd_topn_rows(_ptr(block), int(n_img), int(rows_per_img), int(n_cls), int(ld), int(cls_offset), _ptr(count),
-                             _ptr(row_scale), _ptr(row_bias), int(n_top), _ptr(key), L.stream_ptr()), "wd_topn_rows")
+    L.check(LIB.wd_topn_rows(L.ptr(block), int(n_img), int(rows_per_img), int(n_cls), int(ld), int(cls_offset), L.ptr(count),
+                             L.ptr(row_scale), L.ptr(row_bias), int(n_top), L.ptr(key), L.stream_ptr()), "wd_topn_rows")
 
 
 def topn_unpack(key, rows, n_top, slot, scores_out, labels_out) -> None:
-    L.check(LIB.wd_topn_unpack(_ptr(key), int(rows), int(n_top), int(slot), _ptr(scores_out), _ptr(labels_out), L.stream_ptr()),
+    L.check(LIB.wd_topn_unpack(L.ptr(key), int(rows), int(n_top), int(slot), L.ptr(scores_out), L.ptr(labels_out), L.stream_ptr()),
             "wd_topn_unpack")
 
 
 def topn_kept(key, n_top, n_anchor, out_anchors, out_count, max_out, batch, top_scores, top_labels) -> None:
-    L.check(LIB.wd_topn_kept(_ptr(key), int(n_top), int(n_anchor), _ptr(out_anchors), _ptr(out_count), int(max_out), int(batch),
-                             _ptr(top_scores), _ptr(top_labels), L.stream_ptr()), "wd_topn_kept")
+    L.check(LIB.wd_topn_kept(L.ptr(key), int(n_top), int(n_anchor), L.ptr(out_anchors), L.ptr(out_count), int(max_out), int(batch),
+                             L.ptr(top_scores), L.ptr(top_labels), L.stream_ptr()), "wd_topn_kept")

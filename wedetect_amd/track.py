@@ -12,6 +12,7 @@ from typing import Dict, List, Optional, Sequence
 import torch
 
 from . import lib as L
+from .lib import i32, i64, vp
 
 TRACK_ABI_VERSION = 1
 MAX_TRACKS = 256                 # WD_TRACK_MAX_TRACKS
@@ -20,8 +21,16 @@ MAX_DIM = 1024                   # WD_TRACK_MAX_DIM
 STATUS_FULL = 1                  # WD_TRACK_STATUS_FULL
 STATUS_BAD_COUNT = 2             # WD_TRACK_STATUS_BAD_COUNT
 
-EXPORTS = ("wd_track_abi_version", "wd_track_state_bytes", "wd_track_workspace_bytes", "wd_track_reset", "wd_track_step",
-           "wd_track_export")
+SIGNATURES = {
+    "wd_track_abi_version": (None, []),
+    "wd_track_state_bytes": (i64, [i32, i32, i32]),
+    "wd_track_workspace_bytes": (i64, [i32, i32, i32]),
+    "wd_track_reset": (None, [vp, i32, i32, i32, vp, vp]),
+    "wd_track_step": (None, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
+    "wd_track_export": (None, [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+}
+EXPORTS = tuple(SIGNATURES)
+LIB = L.bind("track", TRACK_ABI_VERSION, SIGNATURES)
 
 
 class WdTrackParams(C.Structure):
@@ -66,28 +75,6 @@ class TrackParams:
                              self.ema_vel, int(self.max_age), int(bool(self.match_labels)))
 
 
-def _bind():
-    lib = L.LIB
-    for name in EXPORTS:
-        if not hasattr(lib, name):
-            raise L.WedetectHipMissing(f"{L.LIB_PATH} does not export {name}; rebuild (python -m wedetect_amd.build)")
-    vp, i32 = C.c_void_p, C.c_int32
-    lib.wd_track_abi_version.restype = C.c_int
-    lib.wd_track_state_bytes.restype = C.c_int64
-    lib.wd_track_state_bytes.argtypes = [i32, i32, i32]
-    lib.wd_track_workspace_bytes.restype = C.c_int64
-    lib.wd_track_workspace_bytes.argtypes = [i32, i32, i32]
-    lib.wd_track_reset.argtypes = [vp, i32, i32, i32, vp, vp]
-    lib.wd_track_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]
-    lib.wd_track_export.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    if lib.wd_track_abi_version() != TRACK_ABI_VERSION:
-        raise L.WedetectHipMissing(f"track ABI mismatch: library {lib.wd_track_abi_version()} vs binding {TRACK_ABI_VERSION}; rebuild")
-    return lib
-
-
-LIB = _bind()
-
-
 def check_sizes(n_seq, max_tracks, dim) -> None:
     for name, v, lo, hi in (("n_seq", n_seq, 1, 65535), ("max_tracks", max_tracks, 1, MAX_TRACKS), ("dim", dim, 4, MAX_DIM)):
         if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
@@ -106,7 +93,7 @@ def workspace_bytes(n_seq: int, max_tracks: int, max_out: int) -> int:
 
 def track_reset(state, n_seq: int, max_tracks: int, dim: int, seq_mask=None) -> None:
     """``wd_track_reset`` on the current stream: ``state`` uint8 [state_bytes]; ``seq_mask`` int32 [n_seq] or None (all)."""
-    L.check(LIB.wd_track_reset(L._p(state), int(n_seq), int(max_tracks), int(dim), None if seq_mask is None else L._p(seq_mask),
+    L.check(LIB.wd_track_reset(L.ptr(state), int(n_seq), int(max_tracks), int(dim), L.ptr(seq_mask),
                                L.stream_ptr()), "wd_track_reset")
 
 
@@ -115,17 +102,17 @@ def track_step(state, workspace, boxes, scores, labels, count, embed, n_seq: int
     """``wd_track_step`` on the current stream: ``boxes`` fp32 [n_seq * n_frame, max_out, 4], ``scores`` fp32 / ``labels`` int32
     [n_seq * n_frame, max_out], ``count`` int32 [n_seq * n_frame], ``embed`` fp32 [n_seq * n_frame, max_out, dim]; writes
     ``track_ids`` / ``track_hits`` int32 [n_seq * n_frame, max_out], whole, and updates ``state``."""
-    L.check(LIB.wd_track_step(L._p(state), L._p(workspace), L._p(boxes), L._p(scores), L._p(labels), L._p(count), L._p(embed),
+    L.check(LIB.wd_track_step(L.ptr(state), L.ptr(workspace), L.ptr(boxes), L.ptr(scores), L.ptr(labels), L.ptr(count), L.ptr(embed),
                               int(n_seq), int(n_frame), int(max_out), int(max_tracks), int(dim), C.addressof(params),
-                              L._p(track_ids), L._p(track_hits), L.stream_ptr()), "wd_track_step")
+                              L.ptr(track_ids), L.ptr(track_hits), L.stream_ptr()), "wd_track_step")
 
 
 def track_export(state, n_seq: int, max_tracks: int, dim: int, ids, labels, scores, boxes, hits, misses, seq_info, vel=None, embed=None) -> None:
     """``wd_track_export`` on the current stream: int32 [n_seq, max_tracks] ``ids`` / ``labels`` / ``hits`` / ``misses``, fp32
     ``scores`` [n_seq, max_tracks] and ``boxes`` [n_seq, max_tracks, 4], int32 ``seq_info`` [n_seq, 4] (next_id, n_live, status, 0)
     and, if given, fp32 ``vel`` [n_seq, max_tracks, 4] and ``embed`` [n_seq, max_tracks, dim]; every element is written."""
-    L.check(LIB.wd_track_export(L._p(state), int(n_seq), int(max_tracks), int(dim), L._p(ids), L._p(labels), L._p(scores),
-                                L._p(boxes), L._p(hits), L._p(misses), L._p(seq_info), None if vel is None else L._p(vel), None if embed is None else L._p(embed),
+    L.check(LIB.wd_track_export(L.ptr(state), int(n_seq), int(max_tracks), int(dim), L.ptr(ids), L.ptr(labels), L.ptr(scores),
+                                L.ptr(boxes), L.ptr(hits), L.ptr(misses), L.ptr(seq_info), L.ptr(vel), L.ptr(embed),
                                 L.stream_ptr()), "wd_track_export")
 
 

@@ -10,6 +10,7 @@ from typing import List
 import torch
 
 from . import lib as L
+from .lib import f32, i32, i64, vp
 
 TUNE_ABI_VERSION = 1
 DIM = 768                        # WD_TUNE_DIM
@@ -18,27 +19,15 @@ ROW_TILE = 128                   # WD_TUNE_ROW_TILE
 MAX_SPLIT = 256                  # WD_TUNE_MAX_SPLIT
 BYTES_PER_ROW = DIM * 4 + 8      # a cached row: the embedding, pos_cls and pos_y
 
-EXPORTS = ("wd_tune_abi_version", "wd_tune_plan", "wd_tune_targets", "wd_tune_grad", "wd_tune_update")
-
-
-def _bind():
-    lib = L.LIB
-    for name in EXPORTS:
-        if not hasattr(lib, name):
-            raise L.WedetectHipMissing(f"{L.LIB_PATH} does not export {name}; rebuild (python -m wedetect_amd.build)")
-    vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
-    lib.wd_tune_abi_version.restype = C.c_int
-    lib.wd_tune_plan.restype = i32
-    lib.wd_tune_plan.argtypes = [i64, i32]
-    lib.wd_tune_targets.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]
-    lib.wd_tune_grad.argtypes = [vp, i32, i32, i32, i32, i32, f32, f32, f32, f32, f32, f32, vp, vp, vp, i32, f32, i32, vp, vp, vp]
-    lib.wd_tune_update.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, f32, f32, f32, f32, f32, f32, vp, i32, vp, vp]
-    if lib.wd_tune_abi_version() != TUNE_ABI_VERSION:
-        raise L.WedetectHipMissing(f"tune ABI mismatch: library {lib.wd_tune_abi_version()} vs binding {TUNE_ABI_VERSION}; rebuild")
-    return lib
-
-
-LIB = _bind()
+SIGNATURES = {
+    "wd_tune_abi_version": (None, []),
+    "wd_tune_plan": (i32, [i64, i32]),
+    "wd_tune_targets": (None, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
+    "wd_tune_grad": (None, [vp, i32, i32, i32, i32, i32, f32, f32, f32, f32, f32, f32, vp, vp, vp, i32, f32, i32, vp, vp, vp]),
+    "wd_tune_update": (None, [vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, f32, f32, f32, f32, f32, f32, vp, i32, vp, vp]),
+}
+EXPORTS = tuple(SIGNATURES)
+LIB = L.bind("tune", TUNE_ABI_VERSION, SIGNATURES)
 
 
 def k_pad(n_cls: int) -> int:
@@ -56,8 +45,8 @@ def plan(rows: int, n_cls: int) -> int:
 def tune_targets(sel_anchors, sel_iou, ex_cls, max_ex: int, m: int, batch: int, n_anchor: int, pos_cls, pos_y) -> None:
     """``wd_tune_targets`` on the current stream: ``sel_anchors`` int32 / ``sel_iou`` fp32 [batch, max_ex * m] (wd_exemplar_assign),
     ``ex_cls`` int32 [batch, max_ex]; writes ``pos_cls`` int32 / ``pos_y`` fp32 [batch, n_anchor], whole."""
-    L.check(LIB.wd_tune_targets(L._p(sel_anchors), L._p(sel_iou), L._p(ex_cls), int(max_ex), int(m), int(batch), int(n_anchor),
-                                L._p(pos_cls), L._p(pos_y), L.stream_ptr()), "wd_tune_targets")
+    L.check(LIB.wd_tune_targets(L.ptr(sel_anchors), L.ptr(sel_iou), L.ptr(ex_cls), int(max_ex), int(m), int(batch), int(n_anchor),
+                                L.ptr(pos_cls), L.ptr(pos_y), L.stream_ptr()), "wd_tune_targets")
 
 
 def tune_grad(embed, rows: int, n_anchor: int, off1: int, off2: int, scale, bias, pos_cls, pos_y, bank, n_cls: int, inv_norm: float,
@@ -65,9 +54,9 @@ def tune_grad(embed, rows: int, n_anchor: int, off1: int, off2: int, scale, bias
     """``wd_tune_grad`` on the current stream: one chunk ``embed`` fp32 [rows, 768] with ``pos_cls`` int32 / ``pos_y`` fp32 [rows],
     the three levels' ``scale`` / ``bias`` floats, ``bank`` fp32 [n_cls, 768] unit rows; writes ``slabs`` fp32
     [n_split, k_pad(n_cls), 768] and ``loss_parts`` fp32 [n_split, k_pad(n_cls) / 32], whole."""
-    L.check(LIB.wd_tune_grad(L._p(embed), int(rows), int(dim), int(n_anchor), int(off1), int(off2), float(scale[0]), float(scale[1]),
-                             float(scale[2]), float(bias[0]), float(bias[1]), float(bias[2]), L._p(pos_cls), L._p(pos_y), L._p(bank),
-                             int(n_cls), float(inv_norm), int(n_split), L._p(slabs), L._p(loss_parts), L.stream_ptr()), "wd_tune_grad")
+    L.check(LIB.wd_tune_grad(L.ptr(embed), int(rows), int(dim), int(n_anchor), int(off1), int(off2), float(scale[0]), float(scale[1]),
+                             float(scale[2]), float(bias[0]), float(bias[1]), float(bias[2]), L.ptr(pos_cls), L.ptr(pos_y), L.ptr(bank),
+                             int(n_cls), float(inv_norm), int(n_split), L.ptr(slabs), L.ptr(loss_parts), L.stream_ptr()), "wd_tune_grad")
 
 
 def tune_update(slabs, n_slab: int, loss_parts, n_cls: int, w, m, v, bank, trainable, lr: float, beta1: float, beta2: float, eps: float,
@@ -77,9 +66,9 @@ def tune_update(slabs, n_slab: int, loss_parts, n_cls: int, w, m, v, bank, train
     rows of ``bank``, writes ``loss_out[step]`` and sets ``status[0]`` on a bad norm."""
     t = int(step) + 1
     beta1, beta2 = C.c_float(beta1).value, C.c_float(beta2).value           # the corrections use the betas the kernel receives: fp32
-    L.check(LIB.wd_tune_update(L._p(slabs), int(n_slab), L._p(loss_parts), int(n_cls), int(dim), L._p(w), L._p(m), L._p(v), L._p(bank),
-                               L._p(trainable), float(lr), beta1, beta2, float(eps), 1.0 - beta1 ** t, 1.0 - beta2 ** t, L._p(loss_out),
-                               int(step), L._p(status), L.stream_ptr()), "wd_tune_update")
+    L.check(LIB.wd_tune_update(L.ptr(slabs), int(n_slab), L.ptr(loss_parts), int(n_cls), int(dim), L.ptr(w), L.ptr(m), L.ptr(v), L.ptr(bank),
+                               L.ptr(trainable), float(lr), beta1, beta2, float(eps), 1.0 - beta1 ** t, 1.0 - beta2 ** t, L.ptr(loss_out),
+                               int(step), L.ptr(status), L.stream_ptr()), "wd_tune_update")
 
 
 def check_bank(bank, what: str = "init_bank") -> torch.Tensor:

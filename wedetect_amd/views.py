@@ -3,9 +3,8 @@ flips a batch of [n, h, w, 3] images in one launch, ``wd_views_merge`` turns the
 rows of that image.  Like feed.py and tile.py: a version and an export list of its own, the main ABI stays as it is."""
 from __future__ import annotations
 
-import ctypes as C
-
 from . import lib as L
+from .lib import f32, i32, i64, vp
 
 VIEWS_ABI_VERSION = 1
 MERGE_MAX_VIEWS = 8
@@ -13,26 +12,14 @@ MERGE_MAX_ROWS = 4096            # n_view * max_in of one image
 MERGE_MAX_OUT = 1024
 FLIP_CODES = {None: 0, "horizontal": 1, "vertical": 2, "diagonal": 3}      # mmcv imflip directions -> WD_FLIP_*
 
-EXPORTS = ("wd_views_abi_version", "wd_flip_u8", "wd_views_merge_workspace_bytes", "wd_views_merge")
-
-
-def _bind():
-    lib = L.LIB
-    for name in EXPORTS:
-        if not hasattr(lib, name):
-            raise L.WedetectHipMissing(f"{L.LIB_PATH} does not export {name}; rebuild (python -m wedetect_amd.build)")
-    vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
-    lib.wd_views_abi_version.restype = C.c_int
-    lib.wd_flip_u8.argtypes = [vp, vp, i32, i32, i32, i32, vp]
-    lib.wd_views_merge_workspace_bytes.restype = i64
-    lib.wd_views_merge_workspace_bytes.argtypes = [i32, i32, i32]
-    lib.wd_views_merge.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp]
-    if lib.wd_views_abi_version() != VIEWS_ABI_VERSION:
-        raise L.WedetectHipMissing(f"views ABI mismatch: library {lib.wd_views_abi_version()} vs binding {VIEWS_ABI_VERSION}; rebuild")
-    return lib
-
-
-LIB = _bind()
+SIGNATURES = {
+    "wd_views_abi_version": (None, []),
+    "wd_flip_u8": (None, [vp, vp, i32, i32, i32, i32, vp]),
+    "wd_views_merge_workspace_bytes": (i64, [i32, i32, i32]),
+    "wd_views_merge": (None, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp]),
+}
+EXPORTS = tuple(SIGNATURES)
+LIB = L.bind("views", VIEWS_ABI_VERSION, SIGNATURES)
 
 
 def merge_workspace_bytes(n_view: int, batch: int, max_in: int) -> int:
@@ -62,5 +49,5 @@ def views_merge(boxes, scores, labels, counts, view_flip, img_wh, n_view: int, b
     L.check(LIB.wd_views_merge(boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(), counts.data_ptr(), view_flip.data_ptr(),
                                img_wh.data_ptr(), int(n_view), int(batch), int(max_in), int(n_cls), L.nms_threshold(iou_thr, L.NMS_MMCV),
                                int(split_thr), int(max_out), out_boxes.data_ptr(), out_scores.data_ptr(), out_labels.data_ptr(),
-                               out_src.data_ptr(), out_count.data_ptr(), workspace.data_ptr(),
-                               workspace.numel() * workspace.element_size(), L.stream_ptr()), "wd_views_merge")
+                               out_src.data_ptr(), out_count.data_ptr(), workspace.data_ptr(), L.nbytes(workspace),
+                               L.stream_ptr()), "wd_views_merge")
