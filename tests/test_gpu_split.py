@@ -1010,3 +1010,61 @@ def test_fused_mlp_wide_with_the_layernorm_folded_is_bit_identical_to_the_two_la
         assert float((got.double() - ref).abs().max()) < 2e-5 * float(ref.abs().max())
     with pytest.raises(L.WedetectHipError):
         L.mlp_fused_wide_ln(ds, m, 512, 2048, wf1, v, u, stats, wf2, b2, got)
+
+
+# ---- every activation through every pre-split kernel's epilogue, both output forms
+ACT_FORM_SHAPE = (272, 256, 64)       # the smallest m, n, k all five kernels accept (cfg 66: m % 16, n % 256; cfg 64: k % 32); 272 = 256 + 16: a ragged row tile
+ACT_FORM_SPLIT_SCALE = 1.0
+
+
+@pytest.fixture(scope="module")
+def act_form_data():
+    """Inputs of test_presplit_kernels_every_activation_and_form, the float64 reference per activation, and the first output seen
+    per (activation, form) — what every other configuration's output must equal bit for bit.  Built once, never changed."""
+    from wedetect_amd import lib as L
+    m, n, k = ACT_FORM_SHAPE
+    a, w, b = _rand((m, k), 301), _rand((n, k), 302, k ** -0.5), _rand((n,), 303)
+    return dict(xs=_to_split(a), ws=L.split_weights(w), b=b, ref={act: _ref64(a, w, b, act) for act in ("none", "relu", "silu", "gelu")},
+                first={})
+
+
+@pytest.mark.parametrize("cfg", [51, 60, 63, 64, 66])
+@pytest.mark.parametrize("form", ["f32", "csplit"])
+@pytest.mark.parametrize("act", ["none", "relu", "silu", "gelu"])
+def test_presplit_kernels_every_activation_and_form(act, form, cfg, act_form_data):
+    """The activation dispatch of every plain pre-split kernel (register-staged 128 x 128, direct-to-LDS, ping-pong, 256 x 256,
+    128 x 256), fp32 rows and fp16 hi/lo (C-split) output: N(0, 1) data with a bias, on which the four activations differ by
+    O(1) on a large share of the elements, so an arm that instantiates the wrong one fails the float64 comparison; and the
+    kernels run the same MFMA order per accumulator, so for one activation and form all five give the same bits."""
+    from wedetect_amd import lib as L
+    d = act_form_data
+    m, n, k = ACT_FORM_SHAPE
+    c = torch.full((m, n), float("nan"), device="cuda")
+    flags = L.SPLIT_A | (L.SPLIT_C if form == "csplit" else 0)
+    L.conv_gemm(d["xs"], None, d["b"], c, batch=1, hin=1, win=m, cin=k, lda=k, n=n, ldc=n, w_split=d["ws"], split_cfg=cfg, split_flags=flags,
+                act=dict(none=L.ACT_NONE, relu=L.ACT_RELU, silu=L.ACT_SILU, gelu=L.ACT_GELU)[act], c_split_scale=ACT_FORM_SPLIT_SCALE)
+    got = _from_split(c) / ACT_FORM_SPLIT_SCALE if form == "csplit" else c
+    assert_close(f"{act} {form} cfg{cfg}", got, d["ref"][act], 6e-6, 2e-6)
+    first_cfg, first = d["first"].setdefault((act, form), (cfg, c))
+    assert torch.equal(c.view(torch.int32), first.view(torch.int32)), f"{act} {form}: cfg {cfg} differs from cfg {first_cfg}"
+
+
+@pytest.mark.parametrize("cfg", [70, 75])
+@pytest.mark.parametrize("form", ["f32", "csplit"])
+def test_conv3x3_kernels_gelu(form, cfg):
+    """GELU through the 3 x 3 kernels' (row, 8 channels) epilogue — the tap-per-stage kernel (cfg 70) and the row-sharing one
+    (cfg 75); CONV_PP_CASES has none / relu / silu only — against a float64 convolution of the same (hi + lo) operands:
+    several row tiles with a ragged last one, n no multiple of the column tile."""
+    from wedetect_amd import lib as L
+    b_, h, w_, ci, co = 2, 19, 23, 48, 136
+    x = _rand((b_ * h * w_, ci), 311)
+    wrow = _rand((co, 9 * ci), 312, (9 * ci) ** -0.5)
+    bias = _rand((co,), 313)
+    xs = _to_split(x)
+    c = torch.full((b_ * h * w_, co), float("nan"), device="cuda")
+    L.conv_gemm(xs, None, bias, c, batch=b_, hin=h, win=w_, cin=ci, lda=ci, kh=3, kw=3, stride=1, pad=1, n=co, ldc=co, act=L.ACT_GELU,
+                w_split=L.split_weights(wrow), split_flags=L.SPLIT_A | (L.SPLIT_C if form == "csplit" else 0), split_cfg=cfg)
+    xd = _from_split(xs).view(b_, h, w_, ci).permute(0, 3, 1, 2)
+    wd = wrow.double().view(co, 3, 3, ci).permute(0, 3, 1, 2)
+    ref = torch.nn.functional.gelu(torch.nn.functional.conv2d(xd, wd, bias.double(), padding=1)).permute(0, 2, 3, 1).reshape(b_ * h * w_, co)
+    assert_close(f"3x3 gelu {form} cfg{cfg}", _from_split(c) if form == "csplit" else c, ref, 6e-6, 2e-6)

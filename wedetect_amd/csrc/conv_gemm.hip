@@ -29,7 +29,7 @@
 //   configuration therefore sums k in the same order and results are bit-identical across them.
 //   Workgroups are renumbered so that each XCD (b % 8) walks a contiguous range of tiles: the
 //   column tiles that share an A row panel hit the same L2.
-#include "common.h"
+#include "gemm_prims.h"
 #include "gemm_loader.h"
 #include "gemm_core.h"
 
@@ -177,14 +177,7 @@ __global__ void __launch_bounds__(64 * WM * WN, min_waves_per_simd(WM * WN, TM *
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int wm = wave / WN, wn = wave % WN;
-  int tile = blockIdx.x;
-  if (VAR & VAR_XCD) {
-    // workgroup b runs on XCD b % 8 (observed; only locality depends on it).  Give XCD x the
-    // contiguous tile range [start(x), start(x+1)): bijective for any grid size.
-    const int nwg = gridDim.x, xcd = tile & 7, idx = tile >> 3;
-    const int q = nwg >> 3, r = nwg & 7;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int tile = (VAR & VAR_XCD) ? wd_xcd_tile(blockIdx.x, gridDim.x) : blockIdx.x;
   const int bn = tile % nbn, bm = tile / nbn;
   const int m0 = bm * T::BM, n0 = bn * T::BN;
 
@@ -208,21 +201,8 @@ __global__ void __launch_bounds__(64 * WM * WN, min_waves_per_simd(WM * WN, TM *
   const bool special = p.out_mode != WD_OUT_ROWS || p.c_batch_stride > 0 || p.seg_rows > 0 || p.sigmoid ||
                        p.out_scale != 1.0f || p.out_bias != 0.0f;
   EpiCtx ec{m0, n0, wm, wn, lane, vec_c, vec_res, vec_bias};
-  if (special) {
-    switch (p.act) {
-      case WD_ACT_RELU: epilogue<TM, TN, WD_ACT_RELU, true>(p, ec, acc); break;
-      case WD_ACT_SILU: epilogue<TM, TN, WD_ACT_SILU, true>(p, ec, acc); break;
-      case WD_ACT_GELU: epilogue<TM, TN, WD_ACT_GELU, true>(p, ec, acc); break;
-      default: epilogue<TM, TN, WD_ACT_NONE, true>(p, ec, acc); break;
-    }
-  } else {
-    switch (p.act) {
-      case WD_ACT_RELU: epilogue<TM, TN, WD_ACT_RELU, false>(p, ec, acc); break;
-      case WD_ACT_SILU: epilogue<TM, TN, WD_ACT_SILU, false>(p, ec, acc); break;
-      case WD_ACT_GELU: epilogue<TM, TN, WD_ACT_GELU, false>(p, ec, acc); break;
-      default: epilogue<TM, TN, WD_ACT_NONE, false>(p, ec, acc); break;
-    }
-  }
+  if (special) WD_ACT_DISPATCH(p.act, epilogue<TM, TN, ACT, true>(p, ec, acc));
+  else WD_ACT_DISPATCH(p.act, epilogue<TM, TN, ACT, false>(p, ec, acc));
 }
 
 // ---------------------------------------------------------------------------------------
@@ -305,18 +285,16 @@ int launch_cfg(const WdConvGemm& p, hipStream_t st) {
   const int nbm = (p.m + T::BM - 1) / T::BM, nbn = (p.n + T::BN - 1) / T::BN;
   const long long nblk = (long long)nbm * nbn;
   if (nblk <= 0 || nblk > 0x7fffffffLL) return WD_ERR_BAD_ARG;
-  const int vec_c = (p.ldc % 4 == 0) && wd_aligned16(p.c) && (p.out_mode == WD_OUT_ROWS || (p.n % 16 == 0));
-  const int vec_res = p.res ? ((p.ldres % 4 == 0) && wd_aligned16(p.res)) : 0;
-  const int vec_bias = p.bias ? wd_aligned16(p.bias) : 0;
+  const WdEpiVecFlags vf = wd_epi_vec_flags(p, true);
   static WdAttrOnce attr_plain, attr_conv;
   if (conv) {
     auto k = conv_gemm_kernel<TM, TN, WM, WN, true, BKT, VAR>;
     if (wd_set_max_lds(attr_conv, reinterpret_cast<const void*>(k), T::LDS_BYTES) != WD_OK) return WD_ERR_LAUNCH;
-    WD_LAUNCH_GEMM(k, dim3((unsigned)nblk), dim3(T::NT), T::LDS_BYTES, st, p, nbn, vec_c, vec_res, vec_bias);
+    WD_LAUNCH_GEMM(k, dim3((unsigned)nblk), dim3(T::NT), T::LDS_BYTES, st, p, nbn, vf.c, vf.res, vf.bias);
   } else {
     auto k = conv_gemm_kernel<TM, TN, WM, WN, false, BKT, VAR>;
     if (wd_set_max_lds(attr_plain, reinterpret_cast<const void*>(k), T::LDS_BYTES) != WD_OK) return WD_ERR_LAUNCH;
-    WD_LAUNCH_GEMM(k, dim3((unsigned)nblk), dim3(T::NT), T::LDS_BYTES, st, p, nbn, vec_c, vec_res, vec_bias);
+    WD_LAUNCH_GEMM(k, dim3((unsigned)nblk), dim3(T::NT), T::LDS_BYTES, st, p, nbn, vf.c, vf.res, vf.bias);
   }
   return wd_launch_status();
 }

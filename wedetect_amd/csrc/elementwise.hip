@@ -3,7 +3,7 @@
 // per-lane accesses with lanes running along the channel axis (coalesced 1 KiB per wave
 // instruction whenever C >= 256).
 #include <stdlib.h>
-#include "common.h"
+#include "gemm_prims.h"
 
 namespace {
 
@@ -273,10 +273,6 @@ constexpr int DM_WG = 7;                                   // the 49 taps: 7 gro
 constexpr int DM_LDS_FLOATS = DM_TIN + DM_WG * 8 * DT_CB;  // 48 KB: three workgroups per CU
 constexpr int DM_NI = (DM_AG + 3) / 4;                     // activation instructions per wave (11; the last only for wave 0)
 
-__device__ __forceinline__ void dm_dma(unsigned lds_addr, const void* src) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(lds_addr), "v"(src) : "memory", "m0");
-}
-
 // One thread's share of the tile's LDS-DMA: instruction i of wave v fills slots [8 (v + 4 i), + 8) (lane = (slot in the group,
 // channel quad)); init() once per spatial tile, issue() once per channel block (waits for the wave's own requests; the caller's
 // barrier makes everybody's visible).
@@ -311,10 +307,10 @@ struct DmStage {
   __device__ __forceinline__ void issue(const unsigned char* xq, const unsigned char* wq, const unsigned char* zp) const {
     static_assert(DM_AG == 4 * (DM_NI - 1) + 1 && DM_WG == 7, "groups 0..39 by all four waves, group 40 by wave 0; tap groups 0..3 by all, 4..6 by waves 0..2");
 #pragma unroll
-    for (int i = 0; i < DM_NI - 1; ++i) dm_dma(la + i * 4096, ((okm >> i) & 1u) ? xq + voff[i] : zp);
-    dm_dma(la + DM_TIN * 4, ((okm >> 16) & 1u) ? wq + woff[0] : zp);
-    if (wave == 0) dm_dma(la + (DM_NI - 1) * 4096, ((okm >> (DM_NI - 1)) & 1u) ? xq + voff[DM_NI - 1] : zp);     // wave-uniform
-    if (wave < 3) dm_dma(la + DM_TIN * 4 + 4096, ((okm >> 17) & 1u) ? wq + woff[1] : zp);
+    for (int i = 0; i < DM_NI - 1; ++i) wd_lds_dma_vaddr_nop(la + i * 4096, ((okm >> i) & 1u) ? xq + voff[i] : zp);
+    wd_lds_dma_vaddr_nop(la + DM_TIN * 4, ((okm >> 16) & 1u) ? wq + woff[0] : zp);
+    if (wave == 0) wd_lds_dma_vaddr_nop(la + (DM_NI - 1) * 4096, ((okm >> (DM_NI - 1)) & 1u) ? xq + voff[DM_NI - 1] : zp);     // wave-uniform
+    if (wave < 3) wd_lds_dma_vaddr_nop(la + DM_TIN * 4 + 4096, ((okm >> 17) & 1u) ? wq + woff[1] : zp);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
 };
@@ -737,11 +733,7 @@ __global__ void __launch_bounds__(256) layernorm_rows_kernel(const float* __rest
 // share input (halo rows / columns) renumber their workgroups so that each XCD walks a CONTIGUOUS run of tiles — the same
 // renumbering as the GEMM kernels' — instead of every eighth one: with the plain order the stage-1 dwconv + LayerNorm kernel
 // fetched 962 MB per launch for its 419 MB input (profiles/r04_traffic.json: every halo pixel came over the fabric once per
-// tile that touches it, because the tile next door ran on another XCD).
-__device__ __forceinline__ int wd_xcd_contiguous(int bid, int nwg) {
-  const int xcd = bid & 7, idx = bid >> 3, q = nwg >> 3, r = nwg & 7;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-}
+// tile that touches it, because the tile next door ran on another XCD).  The renumbering is wd_xcd_tile (gemm_prims.h).
 
 // ---------------------------------------------------------------------------------------
 // depthwise 7x7 + LayerNorm in ONE kernel (ConvNeXt Block: dwconv -> permute -> norm, mm_backbone.py:113-116).
@@ -761,7 +753,7 @@ __global__ void __launch_bounds__(256) dwconv7_ln_kernel(const float* __restrict
   float* tw = lds + DT_IH * DT_IWP * DT_CP;
   const int t = threadIdx.x;
   const int ncb = c / DT_CB;
-  int bid = wd_xcd_contiguous(blockIdx.x, gridDim.x);
+  int bid = wd_xcd_tile(blockIdx.x, gridDim.x);
   const int tx = bid % tiles_w; bid /= tiles_w;
   const int ty = bid % tiles_h;
   const long long b = bid / tiles_h;
@@ -921,7 +913,7 @@ __global__ void __launch_bounds__(256) dwconv7_ln_reg_kernel(const float* __rest
   float* tin = lds;
   float* tw = lds + IH * DS_IWP * DT_CB;
   const int t = threadIdx.x;
-  int bid = wd_xcd_contiguous(blockIdx.x, gridDim.x);
+  int bid = wd_xcd_tile(blockIdx.x, gridDim.x);
   const int tx = bid % tiles_w; bid /= tiles_w;
   const int ty = bid % tiles_h;
   const long long b = bid / tiles_h;
@@ -1002,7 +994,7 @@ __global__ void __launch_bounds__(256) dwconv7_ln_reg4_kernel(const float* __res
   float* tin = lds;
   float* tw = lds + DT_IH * DT_IWP * DT_CP;
   const int t = threadIdx.x;
-  int bid = wd_xcd_contiguous(blockIdx.x, gridDim.x);
+  int bid = wd_xcd_tile(blockIdx.x, gridDim.x);
   const int tx = bid % tiles_w; bid /= tiles_w;
   const int ty = bid % tiles_h;
   const long long b = bid / tiles_h;
@@ -1150,7 +1142,7 @@ __global__ void __launch_bounds__(256 * NG) dwconv7_ln_wide_kernel(const float* 
   const int t = threadIdx.x & 255;
   float* tin = lds_dyn + G * DT_LDS_FLOATS;
   float* tw = tin + DT_IH * DT_IWP * DT_CP;
-  int bid = wd_xcd_contiguous(blockIdx.x, gridDim.x);
+  int bid = wd_xcd_tile(blockIdx.x, gridDim.x);
   const int tx = bid % tiles_w; bid /= tiles_w;
   const int ty = bid % tiles_h;
   const long long b = bid / tiles_h;

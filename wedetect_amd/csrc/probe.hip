@@ -1,11 +1,7 @@
 // probe.hip — diagnostic micro-benchmarks (not on the product path): what the hardware gives the LDS-fed GEMM kernels.
-#include "common.h"
+#include "gemm_prims.h"
 
 namespace {
-
-__device__ __forceinline__ void probe_dma16(unsigned lds_addr, const unsigned char* src) {
-  asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(lds_addr), "v"(src) : "memory", "m0");
-}
 
 // Every wave streams `iters` x 8 LDS-DMA instructions (1 KB each) from its workgroup's window of `window` bytes
 // (walked cyclically: a small window is cache-resident, a large one streams from HBM) into the workgroup's LDS ring,
@@ -26,7 +22,7 @@ __global__ void __launch_bounds__(512) lds_dma_probe_kernel(const unsigned char*
     for (int j = 0; j < 8; ++j) {
       if (off + span > window) off -= (window / step) * step;
       if (off < 0) off = 0;
-      probe_dma16(__builtin_amdgcn_readfirstlane(lds0 + ((it & 1) * 8 + j) * 1024), base + off + lane_off);
+      wd_lds_dma_vaddr(__builtin_amdgcn_readfirstlane(lds0 + ((it & 1) * 8 + j) * 1024), base + off + lane_off);
       off += step;
     }
     asm volatile("s_waitcnt vmcnt(8)" ::: "memory");

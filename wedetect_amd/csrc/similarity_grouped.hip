@@ -19,7 +19,7 @@
 // >= count[b] (gemm_mainloop's n < N guard) and masks them in the epilogue.  The filler is +0.0f by contract:
 // wd_topk_candidates keeps score > thr with thr >= 0 and orders scores by bit pattern, so padding never becomes a candidate.
 // All stores are vector stores from VGPRs (16 bytes where ldo and the pointer allow it, 4 bytes otherwise).
-#include "common.h"
+#include "gemm_prims.h"
 #include "gemm_loader.h"
 #include "gemm_core.h"
 
@@ -70,12 +70,7 @@ __global__ void __launch_bounds__(64 * WM * WN, 5) similarity_grouped_kernel(con
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int wm = wave / WN, wn = wave % WN;
-  int tile = blockIdx.x;
-  if (VAR & VAR_XCD) {   // conv_gemm.hip: XCD x = blockIdx % 8 walks the contiguous tile range [start(x), start(x + 1))
-    const int nwg = gridDim.x, xcd = tile & 7, idx = tile >> 3;
-    const int q = nwg >> 3, r = nwg & 7;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int tile = (VAR & VAR_XCD) ? wd_xcd_tile(blockIdx.x, gridDim.x) : blockIdx.x;
   const int bn = tile % a.nbn;
   const int rest = tile / a.nbn;
   const int bm = rest % a.nbm, img = rest / a.nbm;      // img < n_img: the grid is exactly n_img * nbm * nbn workgroups

@@ -189,23 +189,8 @@ __device__ __forceinline__ void epi_oct_all(const WdConvGemm& p, float unscale, 
                        p.out_scale != 1.0f || p.out_bias != 0.0f;
   EpiOctOperands<TM, TN, PRE> ops;
   ops.load(p, mw, nw, lane);
-#define WD_OCT(A, S) EpiOctWalk<0, TM, TN, A, S, CSPLIT, PRE>::run(p, unscale, mw, nw, lane, acc, patch, ops)
-  if (special) {
-    switch (p.act) {
-      case WD_ACT_RELU: WD_OCT(WD_ACT_RELU, true); break;
-      case WD_ACT_SILU: WD_OCT(WD_ACT_SILU, true); break;
-      case WD_ACT_GELU: WD_OCT(WD_ACT_GELU, true); break;
-      default: WD_OCT(WD_ACT_NONE, true); break;
-    }
-  } else {
-    switch (p.act) {
-      case WD_ACT_RELU: WD_OCT(WD_ACT_RELU, false); break;
-      case WD_ACT_SILU: WD_OCT(WD_ACT_SILU, false); break;
-      case WD_ACT_GELU: WD_OCT(WD_ACT_GELU, false); break;
-      default: WD_OCT(WD_ACT_NONE, false); break;
-    }
-  }
-#undef WD_OCT
+  if (special) WD_ACT_DISPATCH(p.act, EpiOctWalk<0, TM, TN, ACT, true, CSPLIT, PRE>::run(p, unscale, mw, nw, lane, acc, patch, ops));
+  else WD_ACT_DISPATCH(p.act, EpiOctWalk<0, TM, TN, ACT, false, CSPLIT, PRE>::run(p, unscale, mw, nw, lane, acc, patch, ops));
 }
 
 }  // namespace

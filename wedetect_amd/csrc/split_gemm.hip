@@ -64,15 +64,8 @@ template <bool SPECIAL>
 int launch_reduce(const WdConvGemm& p, const float* ws, int splits, float unscale, hipStream_t st) {
   const long long total = (long long)p.m * (p.n >> 2);
   const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-  const int vec_c = (p.ldc % 4 == 0) && wd_aligned16(p.c) && (p.out_mode == WD_OUT_ROWS || (p.n % 16 == 0));
-  const int vec_res = p.res ? ((p.ldres % 4 == 0) && wd_aligned16(p.res)) : 0;
-  const int vec_bias = p.bias ? wd_aligned16(p.bias) : 0;
-  switch (p.act) {
-    case WD_ACT_RELU: hipLaunchKernelGGL((splitk_reduce_kernel<WD_ACT_RELU, SPECIAL>), grid, block, 0, st, p, ws, splits, unscale, vec_c, vec_res, vec_bias); break;
-    case WD_ACT_SILU: hipLaunchKernelGGL((splitk_reduce_kernel<WD_ACT_SILU, SPECIAL>), grid, block, 0, st, p, ws, splits, unscale, vec_c, vec_res, vec_bias); break;
-    case WD_ACT_GELU: hipLaunchKernelGGL((splitk_reduce_kernel<WD_ACT_GELU, SPECIAL>), grid, block, 0, st, p, ws, splits, unscale, vec_c, vec_res, vec_bias); break;
-    default: hipLaunchKernelGGL((splitk_reduce_kernel<WD_ACT_NONE, SPECIAL>), grid, block, 0, st, p, ws, splits, unscale, vec_c, vec_res, vec_bias); break;
-  }
+  const WdEpiVecFlags vf = wd_epi_vec_flags(p, true);
+  WD_ACT_DISPATCH(p.act, hipLaunchKernelGGL((splitk_reduce_kernel<ACT, SPECIAL>), grid, block, 0, st, p, ws, splits, unscale, vf.c, vf.res, vf.bias));
   return wd_launch_status();
 }
 
@@ -188,8 +181,14 @@ extern "C" const char* wd_conv_gemm_split_config(int32_t m, int32_t n, int32_t k
 
 // K splits for an under-filled launch: few tiles and a long K loop are latency-bound (one workgroup walks
 // K serially); S workgroups per tile walk K / S each and a second pass adds the partial sums.
+// No split-K form exists for: hi/lo (C-split) output, n that is no whole number of quads (the second pass adds quads), and the
+// kernels without a partial-sum epilogue — the prefetch-distance-2 tile (55), ping-pong (63), and everything from 64 up.
+static bool ksplit_excluded(const WdConvGemm& p, int cfg, int flags) {
+  return (flags & WD_SPLIT_C) || (p.n & 3) || cfg == 55 || cfg == 63 || cfg >= 64;
+}
+
 static int pick_ksplits(const WdConvGemm& p, int cfg, int flags, long long ws_floats) {
-  if (ws_floats <= 0 || (flags & WD_SPLIT_C) || (p.n & 3) || cfg == 55 || cfg == 63 || cfg >= 64) return 1;
+  if (ws_floats <= 0 || ksplit_excluded(p, cfg, flags)) return 1;
   const int bm = 128, bn = (cfg == 52 || cfg == 53) ? 64 : 128, bk = (cfg == 50) ? 32 : 16;
   const long long tiles = (long long)((p.m + (cfg == 52 ? 255 : bm - 1)) / (cfg == 52 ? 256 : bm)) * ((p.n + bn - 1) / bn);
   const int nk = (p.k + bk - 1) / bk;
@@ -288,7 +287,7 @@ static int conv_gemm_split_impl(const WdConvGemm* pp, const void* w_split, float
     if (splits > nk) splits = nk;                             // never an empty split
   }
   if (splits > 1) {
-    if ((flags & WD_SPLIT_C) || (p.n & 3) || cfg == 55 || cfg == 63 || cfg >= 64) return WD_ERR_UNSUPPORTED;
+    if (ksplit_excluded(p, cfg, flags)) return WD_ERR_UNSUPPORTED;
     if ((long long)splits * p.m * p.n > ws_floats) return WD_ERR_WORKSPACE;
   }
   int lrc;

@@ -26,10 +26,6 @@ namespace {
 
 constexpr int CV_BM = 256, CV_WROWS = 128, CV_ROWB = 64, CV_STAGE = (CV_BM + CV_WROWS) * CV_ROWB, CV_NI = 3;
 
-__device__ __forceinline__ void cv_dma16(unsigned lds_addr, const unsigned char* src) {
-  asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(lds_addr), "v"(src) : "memory", "m0");
-}
-
 // wave-uniform: let the newest `groups` DMA groups (CV_NI instructions each) stay outstanding
 __device__ __forceinline__ void cv_wait_groups(int groups) {
   if (groups <= 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -55,12 +51,7 @@ split_conv_pp_kernel(const WdConvGemm p, const unsigned char* __restrict__ wsp, 
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int group = wave >> 2, wm = (wave >> 1) & 1, wn = wave & 1;
-  int tile = blockIdx.x;
-  {
-    const int nwg = gridDim.x, xcd = tile & 7, idx = tile >> 3;
-    const int q = nwg >> 3, r = nwg & 7;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  int tile = wd_xcd_tile(blockIdx.x, gridDim.x);
   const int ntiles = gridDim.x / ksplits;
   const int ks = tile / ntiles;
   tile -= ks * ntiles;
@@ -130,7 +121,7 @@ split_conv_pp_kernel(const WdConvGemm p, const unsigned char* __restrict__ wsp, 
       const bool is_a = (wave * NI + j) * 16 < BM;                     // wave-uniform
       const int off = is_a ? a_off : i_w;
       const unsigned bit = is_a ? (mask[j] >> i_tap) & 1u : mask[j] & 1u;
-      cv_dma16(__builtin_amdgcn_readfirstlane(lbase + j * 1024), bit ? base[j] + off : zp);
+      wd_lds_dma_vaddr(__builtin_amdgcn_readfirstlane(lbase + j * 1024), bit ? base[j] + off : zp);
     }
     i_w += ROWB;
     i_ci += 16;
@@ -288,23 +279,8 @@ int launch_oct_reduce(const WdConvGemm& p, const float* ws, int splits, float un
   const dim3 grid((unsigned)((total + 255) / 256)), block(256);
   const bool special = p.out_mode != WD_OUT_ROWS || p.c_batch_stride > 0 || p.seg_rows > 0 || p.sigmoid ||
                        p.out_scale != 1.0f || p.out_bias != 0.0f;
-#define WD_RED(A, S) hipLaunchKernelGGL((splitk_oct_reduce_kernel<A, S, CSPLIT>), grid, block, 0, st, p, ws, splits, unscale)
-  if (special) {
-    switch (p.act) {
-      case WD_ACT_RELU: WD_RED(WD_ACT_RELU, true); break;
-      case WD_ACT_SILU: WD_RED(WD_ACT_SILU, true); break;
-      case WD_ACT_GELU: WD_RED(WD_ACT_GELU, true); break;
-      default: WD_RED(WD_ACT_NONE, true); break;
-    }
-  } else {
-    switch (p.act) {
-      case WD_ACT_RELU: WD_RED(WD_ACT_RELU, false); break;
-      case WD_ACT_SILU: WD_RED(WD_ACT_SILU, false); break;
-      case WD_ACT_GELU: WD_RED(WD_ACT_GELU, false); break;
-      default: WD_RED(WD_ACT_NONE, false); break;
-    }
-  }
-#undef WD_RED
+  if (special) WD_ACT_DISPATCH(p.act, hipLaunchKernelGGL((splitk_oct_reduce_kernel<ACT, true, CSPLIT>), grid, block, 0, st, p, ws, splits, unscale));
+  else WD_ACT_DISPATCH(p.act, hipLaunchKernelGGL((splitk_oct_reduce_kernel<ACT, false, CSPLIT>), grid, block, 0, st, p, ws, splits, unscale));
   return wd_launch_status();
 }
 

@@ -36,10 +36,6 @@ namespace {
 constexpr int C3_BM = 256, C3_AG = 17;                     // activation rows per tile; DMA groups of 16 staged rows (258 used)
 constexpr int C3_AROWS = C3_AG * 16, C3_ROWB = 64;
 
-__device__ __forceinline__ void c3_dma16(unsigned lds_addr, const unsigned char* src) {
-  asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(lds_addr), "v"(src) : "memory", "m0");
-}
-
 template <int TN, int NBUF_ = 3>
 struct C3 {
   static constexpr int WROWS = 64 * TN;                    // weight rows per tap
@@ -54,15 +50,6 @@ struct C3 {
   static_assert(NJ == 6 || NJ == 4, "the counted waits of the K loop");
   static_assert(LDS >= 8 * 32 * EPI_LDT * 4, "operand LDS must hold one epilogue patch per wave");
 };
-
-#define C3_BARRIER()                          \
-  do {                                        \
-    __builtin_amdgcn_sched_barrier(0);        \
-    asm volatile("" ::: "memory");            \
-    __builtin_amdgcn_s_barrier();             \
-    asm volatile("" ::: "memory");            \
-    __builtin_amdgcn_sched_barrier(0);        \
-  } while (0)
 
 // STAG (round 6): the K loop of the 256 x 256 MLP kernel (split_gemm_p8.hip) applied to this one.  In the plain form all eight
 // waves walk [DMA issue | 3 x (8 ds_reads, 12 MFMAs) | vmcnt | barrier] in step, so the two waves of a SIMD read LDS at the same time
@@ -83,12 +70,7 @@ split_conv3_kernel(const WdConvGemm p, const unsigned char* __restrict__ wsp, co
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int group = wave >> 2, wm = (wave >> 1) & 1, wn = wave & 1;
-  int tile = blockIdx.x;
-  {
-    const int nwg = gridDim.x, xcd = tile & 7, idx = tile >> 3;
-    const int q = nwg >> 3, r = nwg & 7;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  int tile = wd_xcd_tile(blockIdx.x, gridDim.x);
   const int ntiles = gridDim.x / ksplits;
   const int ks = tile / ntiles;
   tile -= ks * ntiles;
@@ -155,7 +137,7 @@ split_conv3_kernel(const WdConvGemm p, const unsigned char* __restrict__ wsp, co
     for (int j = J0; j < J1; ++j) {
       const int off = kind[j] == 0 ? a_off : w_off + tapoff[j];
       const unsigned bit = kind[j] == 0 ? (vmask[j] >> i_kh) & 1u : vmask[j] & 1u;
-      c3_dma16(__builtin_amdgcn_readfirstlane(lbase + ldst[j]), bit ? base[j] + off : zp);
+      wd_lds_dma_vaddr(__builtin_amdgcn_readfirstlane(lbase + ldst[j]), bit ? base[j] + off : zp);
     }
     if constexpr (decltype(last_c)::value) {
       i_ci += 16;
@@ -241,11 +223,11 @@ split_conv3_kernel(const WdConvGemm p, const unsigned char* __restrict__ wsp, co
     unsigned long long* trc = (tile == 0 && ks == 0 && (wave & 3) == 0 && ws) ? reinterpret_cast<unsigned long long*>(ws) + (wave >> 2) * 4096 : nullptr;
     int trc_i = 0;
 #define C3_STAMP() do { if (trc && lane == 0 && trc_i < 4096) trc[trc_i] = __builtin_readcyclecounter(); ++trc_i; } while (0)
-#define C3_SBARRIER() do { C3_STAMP(); C3_BARRIER(); C3_STAMP(); } while (0)
+#define C3_SBARRIER() do { C3_STAMP(); WD_WG_BARRIER(); C3_STAMP(); } while (0)
     C3_STAMP();
 #else
 #define C3_STAMP() do {} while (0)
-#define C3_SBARRIER() C3_BARRIER()
+#define C3_SBARRIER() WD_WG_BARRIER()
 #endif
     h8 xh[TM], xl[TM], wh[TN], wl[TN];
     auto rd = [&](const unsigned char* sp, int kw) {
@@ -404,12 +386,7 @@ split_conv3w_kernel(const WdConvGemm p, const unsigned char* __restrict__ wsp, c
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int t = threadIdx.x, lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-  int tile = blockIdx.x;
-  {
-    const int nwg = gridDim.x, xcd = tile & 7, idx = tile >> 3;
-    const int q = nwg >> 3, r = nwg & 7;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  int tile = wd_xcd_tile(blockIdx.x, gridDim.x);
   const int ntiles = gridDim.x / ksplits;
   const int ks = tile / ntiles;
   tile -= ks * ntiles;
@@ -475,7 +452,7 @@ split_conv3w_kernel(const WdConvGemm p, const unsigned char* __restrict__ wsp, c
                                    : (g < T::NG ? (unsigned)(T::A_BYTES + (((g - C3_AG) / T::WG) * T::WROWS + ((g - C3_AG) % T::WG) * 16) * ROWB)
                                                 : (unsigned)(T::STAGE - 1024));
         const unsigned bit = is_a ? (vmask[j] >> i_kh) & 1u : vmask[j] & 1u;
-        c3_dma16(__builtin_amdgcn_readfirstlane(lbase + ldst), bit ? base[j] + (is_a ? a_off : w_off) : zp);
+        wd_lds_dma_vaddr(__builtin_amdgcn_readfirstlane(lbase + ldst), bit ? base[j] + (is_a ? a_off : w_off) : zp);
       }
       i_ci += 16;
       if (i_ci == p.cin) { i_ci = 0; ++i_kh; }

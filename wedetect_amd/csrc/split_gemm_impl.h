@@ -3,7 +3,7 @@
 // already stored as fp16 hi/lo groups by their producers).
 #pragma once
 #include <type_traits>
-#include "common.h"
+#include "gemm_prims.h"
 #include "gemm_loader.h"
 
 namespace {
@@ -478,6 +478,25 @@ __device__ __forceinline__ void split_epilogue_lds(const WdConvGemm& p, const Ep
   EpiLdsWalk<0, TM, TN, ACT, SPECIAL>::run(p, ev, mw, nw, lane, acc, patch);
 }
 
+// The store tail of the kernels that write plain rows through LDS patches (a wave's tile starts at (mw, nw) and is `width`
+// columns wide): fp16 hi/lo output for a CSPLIT kernel; else the residual-prefetch walk with D tiles in flight where it applies
+// (D = 0: the kernel has none); else the plain LDS walk.  The caller asserts that its LDS holds one patch per wave.
+template <int TM, int TN, int D, bool CSPLIT>
+__device__ __forceinline__ void split_store_tail(const WdConvGemm& p, const EpiVec& ev, int mw, int nw, int width, int lane,
+                                                 const f32x16 (&acc)[TM][TN], float* patch) {
+  if constexpr (CSPLIT) {          // host side guarantees: plain rows, bias 16-byte aligned, n % 8 == 0, no residual
+    WD_ACT_DISPATCH(p.act, EpiCsplitWalk<0, TM, TN, ACT>::run(p, ev, mw, nw, lane, acc, patch));
+    return;
+  }
+  if constexpr (D > 0) {
+    if (epi_res_prefetch_ok(p, ev, nw, width) && mw < p.m) {
+      split_epilogue_res_prefetch<TM, TN, D>(p, ev, mw, nw, lane, acc, patch);
+      return;
+    }
+  }
+  WD_ACT_DISPATCH(p.act, split_epilogue_lds<TM, TN, ACT, false>(p, ev, mw, nw, lane, acc, patch));
+}
+
 constexpr int split_waves_per_simd(int waves, int lds_bytes, int acc_tiles, bool two_sets) {
   // resident workgroups are LDS-limited (160 KB per CU); ask for the register budget that fits
   // them, but never squeeze a 128-register accumulator set (64 x 128 wave tiles) below 256 registers
@@ -501,12 +520,7 @@ split_gemm_kernel(const WdConvGemm p, const unsigned char* __restrict__ wsp, con
   unsigned char* Bs = smem_raw + 2 * BM * ROWB;         // weights:     [2][BN][ROWB]
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int wm = wave / WN, wn = wave % WN;
-  int tile = blockIdx.x;
-  if (VAR & SVAR_XCD) {
-    const int nwg = gridDim.x, xcd = tile & 7, idx = tile >> 3;
-    const int q = nwg >> 3, r = nwg & 7;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  int tile = (VAR & SVAR_XCD) ? wd_xcd_tile(blockIdx.x, gridDim.x) : blockIdx.x;
   // split-K (ksplits > 1): workgroup (tile, ks) accumulates K stages [s_begin, s_end) and writes raw partial
   // sums to ws[ks][m][n]; splitk_reduce_kernel adds them in a fixed order and applies the epilogue
   const int ntiles = gridDim.x / ksplits;
@@ -687,49 +701,12 @@ split_gemm_kernel(const WdConvGemm p, const unsigned char* __restrict__ wsp, con
       split_epilogue_lds<TM, TN, WD_ACT_NONE, false>(pr, er, mw, nw, lane, acc, patch);
       return;
     }
-    if (VAR & SVAR_CSPLIT) {          // host side guarantees: plain rows, bias 16-byte aligned, n % 8 == 0, no residual
-      switch (p.act) {
-        case WD_ACT_RELU: EpiCsplitWalk<0, TM, TN, WD_ACT_RELU>::run(p, ev, mw, nw, lane, acc, patch); break;
-        case WD_ACT_SILU: EpiCsplitWalk<0, TM, TN, WD_ACT_SILU>::run(p, ev, mw, nw, lane, acc, patch); break;
-        case WD_ACT_GELU: EpiCsplitWalk<0, TM, TN, WD_ACT_GELU>::run(p, ev, mw, nw, lane, acc, patch); break;
-        default: EpiCsplitWalk<0, TM, TN, WD_ACT_NONE>::run(p, ev, mw, nw, lane, acc, patch); break;
-      }
-      return;
-    }
-#define WD_SPLIT_EPI(A, S) split_epilogue_lds<TM, TN, A, S>(p, ev, mw, nw, lane, acc, patch)
-    if (special) {
-      switch (p.act) {
-        case WD_ACT_RELU: WD_SPLIT_EPI(WD_ACT_RELU, true); break;
-        case WD_ACT_SILU: WD_SPLIT_EPI(WD_ACT_SILU, true); break;
-        case WD_ACT_GELU: WD_SPLIT_EPI(WD_ACT_GELU, true); break;
-        default: WD_SPLIT_EPI(WD_ACT_NONE, true); break;
-      }
-    } else {
-      switch (p.act) {
-        case WD_ACT_RELU: WD_SPLIT_EPI(WD_ACT_RELU, false); break;
-        case WD_ACT_SILU: WD_SPLIT_EPI(WD_ACT_SILU, false); break;
-        case WD_ACT_GELU: WD_SPLIT_EPI(WD_ACT_GELU, false); break;
-        default: WD_SPLIT_EPI(WD_ACT_NONE, false); break;
-      }
-    }
-#undef WD_SPLIT_EPI
+    if (special && !(VAR & SVAR_CSPLIT)) WD_ACT_DISPATCH(p.act, split_epilogue_lds<TM, TN, ACT, true>(p, ev, mw, nw, lane, acc, patch));
+    else split_store_tail<TM, TN, 0, (VAR & SVAR_CSPLIT) != 0>(p, ev, mw, nw, TN * 32, lane, acc, patch);
     return;
   }
-  if (special) {
-    switch (p.act) {
-      case WD_ACT_RELU: split_epilogue<TM, TN, WD_ACT_RELU, true>(p, ev, mw, nw, lane, acc); break;
-      case WD_ACT_SILU: split_epilogue<TM, TN, WD_ACT_SILU, true>(p, ev, mw, nw, lane, acc); break;
-      case WD_ACT_GELU: split_epilogue<TM, TN, WD_ACT_GELU, true>(p, ev, mw, nw, lane, acc); break;
-      default: split_epilogue<TM, TN, WD_ACT_NONE, true>(p, ev, mw, nw, lane, acc); break;
-    }
-  } else {
-    switch (p.act) {
-      case WD_ACT_RELU: split_epilogue<TM, TN, WD_ACT_RELU, false>(p, ev, mw, nw, lane, acc); break;
-      case WD_ACT_SILU: split_epilogue<TM, TN, WD_ACT_SILU, false>(p, ev, mw, nw, lane, acc); break;
-      case WD_ACT_GELU: split_epilogue<TM, TN, WD_ACT_GELU, false>(p, ev, mw, nw, lane, acc); break;
-      default: split_epilogue<TM, TN, WD_ACT_NONE, false>(p, ev, mw, nw, lane, acc); break;
-    }
-  }
+  if (special) WD_ACT_DISPATCH(p.act, split_epilogue<TM, TN, ACT, true>(p, ev, mw, nw, lane, acc));
+  else WD_ACT_DISPATCH(p.act, split_epilogue<TM, TN, ACT, false>(p, ev, mw, nw, lane, acc));
 }
 
 // WHICH: 0 = instantiate the plain (1x1) and the implicit-im2col kernel, 1 = plain only, 2 = conv only
@@ -743,9 +720,7 @@ int launch_split(const WdConvGemm& p, const void* wsp, float unscale, hipStream_
   const long long nblk = (long long)nbm * nbn * ksplits;
   if (nblk <= 0 || nblk > 0x7fffffffLL) return WD_ERR_BAD_ARG;
   const int k16 = (p.k + 15) / 16 * 16;
-  const int vec_c = (p.ldc % 4 == 0) && wd_aligned16(p.c) && (p.out_mode == WD_OUT_ROWS || (p.n % 16 == 0));
-  const int vec_res = p.res ? ((p.ldres % 4 == 0) && wd_aligned16(p.res)) : 0;
-  const int vec_bias = p.bias ? wd_aligned16(p.bias) : 0;
+  const WdEpiVecFlags vf = wd_epi_vec_flags(p, true);
   const unsigned char* w8 = static_cast<const unsigned char*>(wsp);
   const float* zero = wd_zero_block();
   if (!zero) return WD_ERR_LAUNCH;
@@ -754,14 +729,14 @@ int launch_split(const WdConvGemm& p, const void* wsp, float unscale, hipStream_
     auto k = split_gemm_kernel<TM, TN, WM, WN, BKT, true, VAR>;
     if (wd_set_max_lds(attr_conv, reinterpret_cast<const void*>(k), T::LDS_BYTES) != WD_OK) return WD_ERR_LAUNCH;
     WD_LAUNCH_GEMM(k, dim3((unsigned)nblk), dim3(T::NT), T::LDS_BYTES, st, p, w8, zero, k16, unscale, nbn,
-                       vec_c, vec_res, vec_bias, ksplits, ws);
+                       vf.c, vf.res, vf.bias, ksplits, ws);
     return wd_launch_status();
   }
   if constexpr (WHICH != 2) if (!conv) {
     auto k = split_gemm_kernel<TM, TN, WM, WN, BKT, false, VAR>;
     if (wd_set_max_lds(attr_plain, reinterpret_cast<const void*>(k), T::LDS_BYTES) != WD_OK) return WD_ERR_LAUNCH;
     WD_LAUNCH_GEMM(k, dim3((unsigned)nblk), dim3(T::NT), T::LDS_BYTES, st, p, w8, zero, k16, unscale, nbn,
-                       vec_c, vec_res, vec_bias, ksplits, ws);
+                       vf.c, vf.res, vf.bias, ksplits, ws);
   }
   return wd_launch_status();
 }

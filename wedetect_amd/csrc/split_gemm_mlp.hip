@@ -40,11 +40,6 @@ constexpr int MC_VHEAD = 12, MC_VPM = 7;           // VALU instructions ahead of
 static_assert(4 * 32 * EPI_LDT * 4 <= MC_B1, "the epilogue patches reuse the weight rings");
 static_assert(2 * MC_LDS <= 160 * 1024, "two workgroups per CU");
 
-// one 1 KB LDS-DMA: 64 lanes x 16 B from base + voff[lane] to LDS [lds_addr, +1024)
-__device__ __forceinline__ void ml_dma(unsigned lds_addr, unsigned voff, const unsigned char* base) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds_addr), "v"(voff), "s"(base) : "memory", "m0");
-}
-
 struct MlpArgs {
   const unsigned char* a;       // LayerNorm rows as fp16 hi/lo groups [m][128] (row = 512 B)
   const unsigned char* w1;      // split weights [512][128] (row = 512 B)
@@ -102,12 +97,7 @@ __global__ void __launch_bounds__(256, 2) fused_mlp128_kernel(const MlpArgs q) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int t = threadIdx.x, lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-  int tile = blockIdx.x;
-  {
-    const int nwg = gridDim.x, xcd = tile & 7, idx = tile >> 3;
-    const int qq = nwg >> 3, r = nwg & 7;
-    tile = (xcd < r ? xcd * (qq + 1) : r * (qq + 1) + (xcd - r) * qq) + idx;
-  }
+  const int tile = wd_xcd_tile(blockIdx.x, gridDim.x);
   const int m0 = tile * ML_BM + wave * 32;
   const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem_raw;
 
@@ -120,14 +110,14 @@ __global__ void __launch_bounds__(256, 2) fused_mlp128_kernel(const MlpArgs q) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int idx = wave * 4 + i, s = idx >> 1, rg = idx & 1;
-      ml_dma(lds0 + MC_W1 + (j & 1) * MB_W1BUF + s * MB_W1STAGE + rg * 1024, va, q.w1 + (size_t)(j * MB_HC + rg * 16) * 512 + s * 64);
+      wd_lds_dma_sbase(lds0 + MC_W1 + (j & 1) * MB_W1BUF + s * MB_W1STAGE + rg * 1024, va, q.w1 + (size_t)(j * MB_HC + rg * 16) * 512 + s * 64);
     }
   };
   auto issue_w2 = [&](int j) {                       // W2 columns [32 j, +32) -> ring slot j & 1
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int idx = wave * 4 + i, s = idx >> 3, rg = idx & 7;
-      ml_dma(lds0 + MC_W2 + (j & 1) * MB_W2BUF + s * MB_W2STAGE + rg * 1024, vw2, q.w2 + (size_t)(rg * 16) * 2048 + (size_t)(j * 2 + s) * 64);
+      wd_lds_dma_sbase(lds0 + MC_W2 + (j & 1) * MB_W2BUF + s * MB_W2STAGE + rg * 1024, vw2, q.w2 + (size_t)(rg * 16) * 2048 + (size_t)(j * 2 + s) * 64);
     }
   };
   issue_w1(0);

@@ -85,13 +85,6 @@ struct MwArgs {
 // form, whose piece loop keeps enough scalars alive that hipcc still spills SGPRs, pads every asm VMEM instruction with
 // s_nop 4 instead (SAFE = true; ~5 % of its time).
 #define MW_OPAQUE(p) asm volatile("" : "+s"(p))
-template <bool SAFE>
-__device__ __forceinline__ void mw_dma(unsigned lds_addr, unsigned voff, const unsigned char* base) {
-  if constexpr (SAFE)
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 4\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds_addr), "v"(voff), "s"(base) : "memory", "m0");
-  else
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds_addr), "v"(voff), "s"(base) : "memory", "m0");
-}
 
 // Every VMEM operation of the main loop is issued from inline assembly and retired with a COUNTED s_waitcnt: with one wave
 // per SIMD a full vmcnt(0) drain per K tile (the first form of this kernel, 840 us) exposes the whole L2 / Infinity-Cache
@@ -168,10 +161,7 @@ __global__ void __launch_bounds__(256) fused_mlp_wide_kernel(const MwArgs q) {
     first_blk = (int)(u0 / P::NCH); seg_o = (int)(u0 - (long long)first_blk * P::NCH);
     last_blk = (int)(u1 / P::NCH); seg_e = (int)(u1 - (long long)last_blk * P::NCH);
   } else {
-    int tile = blockIdx.x;
-    const int nwg = gridDim.x, xcd = tile & 7, idx = tile >> 3;
-    const int qq = nwg >> 3, r = nwg & 7;
-    tile = (xcd < r ? xcd * (qq + 1) : r * (qq + 1) + (xcd - r) * qq) + idx;
+    const int tile = wd_xcd_tile(blockIdx.x, gridDim.x);
     first_blk = tile; seg_o = 0; last_blk = tile + 1; seg_e = 0;
   }
   // pieces in execution order: [head of the last block] [whole blocks] [tail of the first block]
@@ -192,7 +182,7 @@ __global__ void __launch_bounds__(256) fused_mlp_wide_kernel(const MwArgs q) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const int g = wave * 8 + i;
-      mw_dma<PERSIST>(lds0 + slot * P::XSLOT + g * 1024, la[i & 3], arow + (size_t)(4 * g) * (C * 4) + kt * 256);
+      wd_lds_dma_sbase<PERSIST>(lds0 + slot * P::XSLOT + g * 1024, la[i & 3], arow + (size_t)(4 * g) * (C * 4) + kt * 256);
     }
   };
 

@@ -37,20 +37,6 @@ namespace {
 
 constexpr int P4_ROWB = 64, P4_A = 128 * P4_ROWB, P4_W = 256 * P4_ROWB, P4_SLOT = P4_A + P4_W, P4_LDS = 3 * P4_SLOT;
 
-__device__ __forceinline__ void p4_dma(unsigned lds_addr, unsigned voff, const unsigned char* base) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2"
-               :: "s"(lds_addr), "v"(voff), "s"(base) : "memory", "m0");
-}
-
-#define P4_BARRIER()                          \
-  do {                                        \
-    __builtin_amdgcn_sched_barrier(0);        \
-    asm volatile("" ::: "memory");            \
-    __builtin_amdgcn_s_barrier();             \
-    asm volatile("" ::: "memory");            \
-    __builtin_amdgcn_sched_barrier(0);        \
-  } while (0)
-
 template <int VAR>
 __global__ void __launch_bounds__(256, 2)
 split_gemm_p4_kernel(const WdConvGemm p, const unsigned char* __restrict__ wsp, int k16, float unscale, int nbn,
@@ -62,12 +48,7 @@ split_gemm_p4_kernel(const WdConvGemm p, const unsigned char* __restrict__ wsp, 
   const int nk = p.k >> 4;
 
   // ---- tile of this workgroup: XCD-contiguous ranges of the (column-group-major) tile list
-  int tile = blockIdx.x;
-  {
-    const int nwg = gridDim.x, xcd = tile & 7, idx = tile >> 3;
-    const int q = nwg >> 3, r = nwg & 7;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int tile = wd_xcd_tile(blockIdx.x, gridDim.x);
   const int gsz = ngrp * nbm;
   const int grp = tile / gsz, rem = tile - grp * gsz;
   const int bm = rem / ngrp, bn = grp * ngrp + (rem - bm * ngrp);
@@ -100,7 +81,7 @@ split_gemm_p4_kernel(const WdConvGemm p, const unsigned char* __restrict__ wsp, 
     const int limit = p.m - 16;
     row = row < limit ? row : limit;
     const unsigned char* src = abase + (size_t)row * ((size_t)p.lda * 4u) + (size_t)kt * P4_ROWB;
-    p4_dma(dma_dst + slot * P4_SLOT + half * 4096, la, src);
+    wd_lds_dma_sbase(dma_dst + slot * P4_SLOT + half * 4096, la, src);
   };
   auto stage_w = [&](int kt, int slot, int half) {
 #pragma unroll
@@ -109,7 +90,7 @@ split_gemm_p4_kernel(const WdConvGemm p, const unsigned char* __restrict__ wsp, 
       const int limit = p.n - 16;
       row = row < limit ? row : limit;
       const unsigned char* src = wsp + (size_t)row * ((size_t)k16 * 4u) + (size_t)kt * P4_ROWB;
-      p4_dma(dma_dst + slot * P4_SLOT + P4_A + half * 8192 + j * 4096, lw, src);
+      wd_lds_dma_sbase(dma_dst + slot * P4_SLOT + P4_A + half * 8192 + j * 4096, lw, src);
     }
   };
 
@@ -161,7 +142,7 @@ split_gemm_p4_kernel(const WdConvGemm p, const unsigned char* __restrict__ wsp, 
   do {                                                         \
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");         \
     asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory");      \
-    P4_BARRIER();                                              \
+    WD_WG_BARRIER();                                           \
   } while (0)
 
   // ---- prologue: the requests the steady state would have issued before step 0, in its order; step 0 must have
@@ -175,7 +156,7 @@ split_gemm_p4_kernel(const WdConvGemm p, const unsigned char* __restrict__ wsp, 
   } else {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
-  P4_BARRIER();
+  WD_WG_BARRIER();
 
   // slot of step kt = kt % 3, tracked incrementally: s0 = slot(kt), s2 = slot(kt + 2)
   int s0 = 0, s2 = 2;
@@ -240,7 +221,7 @@ split_gemm_p4_kernel(const WdConvGemm p, const unsigned char* __restrict__ wsp, 
   }
 #undef P4_SYNC
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  P4_BARRIER();                                              // every read of the ring is over: LDS becomes epilogue patches
+  WD_WG_BARRIER();                                           // every read of the ring is over: LDS becomes epilogue patches
 
   const EpiVec ev{vec_c, vec_res, vec_bias, unscale};
   const int mw = m0, nw = n0 + wave * 64;
@@ -248,23 +229,8 @@ split_gemm_p4_kernel(const WdConvGemm p, const unsigned char* __restrict__ wsp, 
   int lane_e = lane;
   asm volatile("" : "+v"(lane_e));          // epilogue address arithmetic starts here, not before the K loop
   static_assert(P4_LDS >= 4 * 32 * EPI_LDT * 4, "operand LDS must hold one patch per wave");
-  if (VAR & SVAR_CSPLIT) {
-    switch (p.act) {
-      case WD_ACT_RELU: EpiCsplitWalk<0, TM, TN, WD_ACT_RELU>::run(p, ev, mw, nw, lane_e, acc, patch); break;
-      case WD_ACT_SILU: EpiCsplitWalk<0, TM, TN, WD_ACT_SILU>::run(p, ev, mw, nw, lane_e, acc, patch); break;
-      case WD_ACT_GELU: EpiCsplitWalk<0, TM, TN, WD_ACT_GELU>::run(p, ev, mw, nw, lane_e, acc, patch); break;
-      default: EpiCsplitWalk<0, TM, TN, WD_ACT_NONE>::run(p, ev, mw, nw, lane_e, acc, patch); break;
-    }
-  } else if (epi_res_prefetch_ok(p, ev, nw, 64)) {
-    split_epilogue_res_prefetch<TM, TN, 3>(p, ev, mw, nw, lane_e, acc, patch);
-  } else {
-    switch (p.act) {
-      case WD_ACT_RELU: split_epilogue_lds<TM, TN, WD_ACT_RELU, false>(p, ev, mw, nw, lane_e, acc, patch); break;
-      case WD_ACT_SILU: split_epilogue_lds<TM, TN, WD_ACT_SILU, false>(p, ev, mw, nw, lane_e, acc, patch); break;
-      case WD_ACT_GELU: split_epilogue_lds<TM, TN, WD_ACT_GELU, false>(p, ev, mw, nw, lane_e, acc, patch); break;
-      default: split_epilogue_lds<TM, TN, WD_ACT_NONE, false>(p, ev, mw, nw, lane_e, acc, patch); break;
-    }
-  }
+  __builtin_assume(mw < p.m);               // mw = m0: the grid holds ceil(m / 128) row blocks
+  split_store_tail<TM, TN, 3, (VAR & SVAR_CSPLIT) != 0>(p, ev, mw, nw, 64, lane_e, acc, patch);
 }
 
 template <int VAR>
@@ -274,16 +240,14 @@ int launch_p4(const WdConvGemm& p, const void* wsp, float unscale, hipStream_t s
   if (nblk <= 0 || nblk > 0x7fffffffLL) return WD_ERR_BAD_ARG;
   const int k16 = (p.k + 15) / 16 * 16;
   if (!wd_dma32_fits(p.m, p.lda, p.n, k16)) return WD_ERR_UNSUPPORTED;   // 32-bit DMA offsets from the operand bases
-  const int vec_c = (p.ldc % 4 == 0) && wd_aligned16(p.c);
-  const int vec_res = p.res ? ((p.ldres % 4 == 0) && wd_aligned16(p.res)) : 0;
-  const int vec_bias = p.bias ? wd_aligned16(p.bias) : 0;
+  const WdEpiVecFlags vf = wd_epi_vec_flags(p, false);
   int ngrp = 2;                                                    // column tiles walked in pairs
   if (ngrp > nbn || nbn % ngrp) ngrp = nbn;
   auto k = split_gemm_p4_kernel<VAR>;
   static WdAttrOnce attr;
   if (wd_set_max_lds(attr, reinterpret_cast<const void*>(k), P4_LDS) != WD_OK) return WD_ERR_LAUNCH;
   WD_LAUNCH_GEMM(k, dim3((unsigned)nblk), dim3(256), P4_LDS, st, p, static_cast<const unsigned char*>(wsp), k16, unscale, nbn,
-                 vec_c, vec_res, vec_bias, ngrp, nbm);
+                 vf.c, vf.res, vf.bias, ngrp, nbm);
   return wd_launch_status();
 }
 

@@ -62,21 +62,7 @@ namespace {
 constexpr int P8_ROWB = 128, P8_REGION = 128 * P8_ROWB, P8_TILE = 3 * P8_REGION, P8_LDS = 2 * P8_TILE + 3 * P8_REGION;
 constexpr int P8_A0 = 0, P8_W1 = P8_REGION, P8_A1 = 2 * P8_REGION, P8_W0RING = 2 * P8_TILE;   // W0 of K tile t: P8_W0RING + (t % 3) * P8_REGION
 
-// one 1 KB LDS-DMA: 64 lanes x 16 B from base + voff[lane] to LDS [lds_addr, +1024)
-__device__ __forceinline__ void p8_dma(unsigned lds_addr, unsigned voff, const unsigned char* base) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2"
-               :: "s"(lds_addr), "v"(voff), "s"(base) : "memory", "m0");
-}
-
-#define P8_KBARRIER() do { if (!(ABL & 8)) P8_BARRIER(); } while (0)
-#define P8_BARRIER()                          \
-  do {                                        \
-    __builtin_amdgcn_sched_barrier(0);        \
-    asm volatile("" ::: "memory");            \
-    __builtin_amdgcn_s_barrier();             \
-    asm volatile("" ::: "memory");            \
-    __builtin_amdgcn_sched_barrier(0);        \
-  } while (0)
+#define P8_KBARRIER() do { if (!(ABL & 8)) WD_WG_BARRIER(); } while (0)
 
 // ABL: timing-only ablations for on-device diagnosis (WRONG results by construction; compiled only with
 // -DWD_DEBUG_ABLATIONS, reachable through cfg 640 + ABL): 1 = no DMA in the K loop, 2 = no ds_reads in the K loop,
@@ -591,6 +577,7 @@ split_gemm_p8_kernel(const WdConvGemm p, const unsigned char* __restrict__ wsp, 
     seg_first_tile = (int)(u0 / nk); seg_o = (int)(u0 - (long long)seg_first_tile * nk);
     seg_last_tile = (int)(u1 / nk); seg_e = (int)(u1 - (long long)seg_last_tile * nk);
   } else {
+    // wd_xcd_tile (gemm_prims.h), spelled out: through the call hipcc assigns this kernel's scalar registers differently
     int tile = blockIdx.x;
     const int nwg = gridDim.x, xcd = tile & 7, idx = tile >> 3;
     const int q = nwg >> 3, r = nwg & 7;
@@ -659,13 +646,13 @@ split_gemm_p8_kernel(const WdConvGemm p, const unsigned char* __restrict__ wsp, 
         int row = is_w ? n0 + (2 * j + (wave >> 2)) * 64 + (wave & 3) * 8 + half * 32 : m0 + j * 128 + wave * 8 + half * 64;
         row = row < limit ? row : limit;                            // whole groups past the end re-read the last one
         const unsigned char* src = base + (size_t)row * pitch + (size_t)(kb + kt) * ROWB;
-        p8_dma(dma_dst + reg + j * 8192, is_w ? lw : la, src);
+        wd_lds_dma_sbase(dma_dst + reg + j * 8192, is_w ? lw : la, src);
       }
     };
 
     f32x16 acc[TM][TN];
     // ---- prologue: K tiles 0 and 1 of the piece (the previous piece's epilogue is done with the LDS)
-    P8_BARRIER();
+    WD_WG_BARRIER();
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt)
       if (kt < nks) {
@@ -695,8 +682,8 @@ split_gemm_p8_kernel(const WdConvGemm p, const unsigned char* __restrict__ wsp, 
       park_src = reinterpret_cast<const unsigned char*>(ps.acc) + (size_t)prev * P8_PARK_BYTES + (unsigned)t * 512u;
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    P8_BARRIER();
-    if (group == 1 && !(ABL & 24)) P8_BARRIER();                   // the second row group runs one barrier behind
+    WD_WG_BARRIER();
+    if (group == 1 && !(ABL & 24)) WD_WG_BARRIER();                // the second row group runs one barrier behind
 
     using I0 = std::integral_constant<int, 0>;
     using I1 = std::integral_constant<int, 1>;
@@ -839,8 +826,8 @@ split_gemm_p8_kernel(const WdConvGemm p, const unsigned char* __restrict__ wsp, 
     } else {
       ktile(0, I2{}, std::false_type{}, std::false_type{});
     }
-    if (group == 0 && !(ABL & 24)) P8_BARRIER();                   // pairs with the extra barrier of group 1
-    P8_BARRIER();                                                  // every read of the operand tiles is over: LDS becomes epilogue patches
+    if (group == 0 && !(ABL & 24)) WD_WG_BARRIER();                // pairs with the extra barrier of group 1
+    WD_WG_BARRIER();                                               // every read of the operand tiles is over: LDS becomes epilogue patches
 
     if (PERSIST && is_head) {
       // park the raw accumulators for the next workgroup of the chain: plain coalesced stores, drained, then ONE
@@ -890,24 +877,16 @@ split_gemm_p8_kernel(const WdConvGemm p, const unsigned char* __restrict__ wsp, 
       if (p.act == WD_ACT_GELU) EpiCsplitDirectWalk<0, TM, TN, WD_ACT_GELU>::run(p, ev, mw, nw, lane_e, acc);
       else EpiCsplitDirectWalk<0, TM, TN, WD_ACT_NONE>::run(p, ev, mw, nw, lane_e, acc);
     } else if (VAR & SVAR_CSPLIT) {
-      switch (p.act) {
-        case WD_ACT_RELU: EpiCsplitWalk<0, TM, TN, WD_ACT_RELU>::run(p, ev, mw, nw, lane_e, acc, patch); break;
-        case WD_ACT_SILU: EpiCsplitWalk<0, TM, TN, WD_ACT_SILU>::run(p, ev, mw, nw, lane_e, acc, patch); break;
-        case WD_ACT_GELU: EpiCsplitWalk<0, TM, TN, WD_ACT_GELU, (ABL & 96)>::run(p, ev, mw, nw, lane_e, acc, patch); break;
-        default: EpiCsplitWalk<0, TM, TN, WD_ACT_NONE>::run(p, ev, mw, nw, lane_e, acc, patch); break;
-      }
+      // (ABL & 96: the timing-only forms of the GELU arm, epi_lds_tile_csplit)
+      WD_ACT_DISPATCH(p.act, EpiCsplitWalk<0, TM, TN, ACT, (ACT == WD_ACT_GELU ? (ABL & 96) : 0)>::run(p, ev, mw, nw, lane_e, acc, patch));
     } else if (epi_res_prefetch_ok(p, ev, nw, 64) && mw < p.m) {
+      // (split_store_tail's chain, spelled out: the scored epilogue below sits between its two last links)
       split_epilogue_res_prefetch<TM, TN, 3>(p, ev, mw, nw, lane_e, acc, patch);
     } else if (!PERSIST && (p.seg_rows > 0 || p.sigmoid || p.out_scale != 1.0f || p.out_bias != 0.0f)) {
       // round 6 (wd_similarity_split): per-level affine + sigmoid of the region x text logits, ragged n; no activation
       split_epilogue_lds<TM, TN, WD_ACT_NONE, true>(p, ev, mw, nw, lane_e, acc, patch);
     } else {
-      switch (p.act) {
-        case WD_ACT_RELU: split_epilogue_lds<TM, TN, WD_ACT_RELU, false>(p, ev, mw, nw, lane_e, acc, patch); break;
-        case WD_ACT_SILU: split_epilogue_lds<TM, TN, WD_ACT_SILU, false>(p, ev, mw, nw, lane_e, acc, patch); break;
-        case WD_ACT_GELU: split_epilogue_lds<TM, TN, WD_ACT_GELU, false>(p, ev, mw, nw, lane_e, acc, patch); break;
-        default: split_epilogue_lds<TM, TN, WD_ACT_NONE, false>(p, ev, mw, nw, lane_e, acc, patch); break;
-      }
+      WD_ACT_DISPATCH(p.act, split_epilogue_lds<TM, TN, ACT, false>(p, ev, mw, nw, lane_e, acc, patch));
     }
   }
 }
@@ -952,9 +931,7 @@ int launch_p8(const WdConvGemm& p, const void* wsp, float unscale, hipStream_t s
   const int k16 = (p.k + 15) / 16 * 16;
   // 32-bit DMA offsets from the operand bases
   if (!wd_dma32_fits(arows > 0 ? arows : p.m, p.lda, wrows > 0 ? wrows : p.n, k16)) return WD_ERR_UNSUPPORTED;
-  const int vec_c = (p.ldc % 4 == 0) && wd_aligned16(p.c);
-  const int vec_res = p.res ? ((p.ldres % 4 == 0) && wd_aligned16(p.res)) : 0;
-  const int vec_bias = p.bias ? wd_aligned16(p.bias) : 0;
+  const WdEpiVecFlags vf = wd_epi_vec_flags(p, false);
   // Column tiles of one row block are walked together, up to eight at a time: the activation panel of a row block is then
   // fetched once for all of them (a pwconv1 with n = 2048 re-read it per pair before: 42.79 -> 42.05 ms per step, same
   // box, three rounds; pairs = 2, the round-2 default until then, and 4 / 8 equal).  Up to 2048 weight rows live per group.
@@ -980,7 +957,7 @@ int launch_p8(const WdConvGemm& p, const void* wsp, float unscale, hipStream_t s
   static WdAttrOnce attr;
   if (wd_set_max_lds(attr, reinterpret_cast<const void*>(k), P8_LDS) != WD_OK) return WD_ERR_LAUNCH;
   WD_LAUNCH_GEMM(k, dim3((unsigned)grid), dim3(512), P8_LDS, st, p, static_cast<const unsigned char*>(wsp), k16, unscale, nbn,
-                 vec_c, vec_res, vec_bias, ngrp, nbm, ps, p8_stagger(), arows > 0 ? arows : p.m, wrows > 0 ? wrows : p.n, ep);
+                 vf.c, vf.res, vf.bias, ngrp, nbm, ps, p8_stagger(), arows > 0 ? arows : p.m, wrows > 0 ? wrows : p.n, ep);
   return wd_launch_status();
 }
 

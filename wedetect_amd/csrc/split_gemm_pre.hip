@@ -39,12 +39,7 @@ split_gemm_glds_kernel(const WdConvGemm p, const unsigned char* __restrict__ wsp
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int wm = wave / WN, wn = wave % WN;
-  int tile = blockIdx.x;
-  {
-    const int nwg = gridDim.x, xcd = tile & 7, idx = tile >> 3;
-    const int q = nwg >> 3, r = nwg & 7;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  int tile = wd_xcd_tile(blockIdx.x, gridDim.x);
   // split-K (ksplits > 1): see split_gemm_kernel
   const int ntiles = gridDim.x / ksplits;
   const int ks = tile / ntiles;
@@ -170,23 +165,7 @@ split_gemm_glds_kernel(const WdConvGemm p, const unsigned char* __restrict__ wsp
   const int mw = m0 + wm * TM * 32, nw = n0 + wn * TN * 32;
   float* patch = reinterpret_cast<float*>(smem_raw) + wave * 32 * EPI_LDT;
   static_assert(2 * STAGE >= 4 * 32 * EPI_LDT * 4, "operand LDS must hold one patch per wave");
-  if (VAR & SVAR_CSPLIT) {
-    switch (p.act) {
-      case WD_ACT_RELU: EpiCsplitWalk<0, TM, TN, WD_ACT_RELU>::run(p, ev, mw, nw, lane, acc, patch); break;
-      case WD_ACT_SILU: EpiCsplitWalk<0, TM, TN, WD_ACT_SILU>::run(p, ev, mw, nw, lane, acc, patch); break;
-      case WD_ACT_GELU: EpiCsplitWalk<0, TM, TN, WD_ACT_GELU>::run(p, ev, mw, nw, lane, acc, patch); break;
-      default: EpiCsplitWalk<0, TM, TN, WD_ACT_NONE>::run(p, ev, mw, nw, lane, acc, patch); break;
-    }
-  } else if (epi_res_prefetch_ok(p, ev, nw, TN * 32) && mw < p.m) {
-    split_epilogue_res_prefetch<TM, TN, 1>(p, ev, mw, nw, lane, acc, patch);
-  } else {
-    switch (p.act) {
-      case WD_ACT_RELU: split_epilogue_lds<TM, TN, WD_ACT_RELU, false>(p, ev, mw, nw, lane, acc, patch); break;
-      case WD_ACT_SILU: split_epilogue_lds<TM, TN, WD_ACT_SILU, false>(p, ev, mw, nw, lane, acc, patch); break;
-      case WD_ACT_GELU: split_epilogue_lds<TM, TN, WD_ACT_GELU, false>(p, ev, mw, nw, lane, acc, patch); break;
-      default: split_epilogue_lds<TM, TN, WD_ACT_NONE, false>(p, ev, mw, nw, lane, acc, patch); break;
-    }
-  }
+  split_store_tail<TM, TN, 1, (VAR & SVAR_CSPLIT) != 0>(p, ev, mw, nw, TN * 32, lane, acc, patch);
 }
 
 template <int BK, int VAR>
@@ -197,9 +176,7 @@ int launch_glds(const WdConvGemm& p, const void* wsp, float unscale, hipStream_t
   const long long nblk = (long long)nbm * nbn * ksplits;
   if (nblk <= 0 || nblk > 0x7fffffffLL) return WD_ERR_BAD_ARG;
   const int k16 = (p.k + 15) / 16 * 16;
-  const int vec_c = (p.ldc % 4 == 0) && wd_aligned16(p.c);
-  const int vec_res = p.res ? ((p.ldres % 4 == 0) && wd_aligned16(p.res)) : 0;
-  const int vec_bias = p.bias ? wd_aligned16(p.bias) : 0;
+  const WdEpiVecFlags vf = wd_epi_vec_flags(p, false);
   const float* zero = wd_zero_block();
   if (!zero) return WD_ERR_LAUNCH;
   // column-tile group of the raster order: 4 (measured: -3 % on the wide pwconv1 layers, whose 4 MB of
@@ -214,7 +191,7 @@ int launch_glds(const WdConvGemm& p, const void* wsp, float unscale, hipStream_t
   static WdAttrOnce attr;
   if (wd_set_max_lds(attr, reinterpret_cast<const void*>(k), LDS) != WD_OK) return WD_ERR_LAUNCH;
   WD_LAUNCH_GEMM(k, dim3((unsigned)nblk), dim3(256), LDS, st, p, static_cast<const unsigned char*>(wsp), zero, k16,
-                     unscale, nbn, vec_c, vec_res, vec_bias, ngrp, nbm, ksplits, ws);
+                     unscale, nbn, vf.c, vf.res, vf.bias, ngrp, nbm, ksplits, ws);
   return wd_launch_status();
 }
 
@@ -242,10 +219,6 @@ int launch_glds(const WdConvGemm& p, const void* wsp, float unscale, hipStream_t
 // at the next ds_read; a wave waits for its own DMAs (vmcnt 0) at the end of its MFMA slot, one
 // full slot after issuing them, which is before any wave reads that stage.
 // ---------------------------------------------------------------------------------------
-__device__ __forceinline__ void dma16(unsigned lds_addr, const unsigned char* src) {
-  asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(lds_addr), "v"(src) : "memory", "m0");
-}
-
 template <int N, int NI>
 __device__ __forceinline__ void wait_dma_groups(int groups_in_flight) {
   // wave-uniform: allow the newest `groups_in_flight` DMA groups (NI instructions each) to stay outstanding
@@ -316,12 +289,7 @@ split_gemm_pingpong_kernel(const WdConvGemm p, const unsigned char* __restrict__
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int group = wave >> 2, wm = (wave >> 1) & 1, wn = wave & 1;
-  int tile = blockIdx.x;
-  {
-    const int nwg = gridDim.x, xcd = tile & 7, idx = tile >> 3;
-    const int q = nwg >> 3, r = nwg & 7;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  }
+  const int tile = wd_xcd_tile(blockIdx.x, gridDim.x);
   const int bn = tile % nbn, bm = tile / nbn;
   const int m0 = bm * BM, n0 = bn * BN;
   const int nk = p.k / BK;
@@ -347,7 +315,7 @@ split_gemm_pingpong_kernel(const WdConvGemm p, const unsigned char* __restrict__
     const unsigned base = lds0 + buf * STAGE + wave * NI * 1024;
 #pragma unroll
     for (int j = 0; j < NI; ++j) {
-      dma16(__builtin_amdgcn_readfirstlane(base + j * 1024), ps[j]);
+      wd_lds_dma_vaddr(__builtin_amdgcn_readfirstlane(base + j * 1024), ps[j]);
       ps[j] += st[j];
     }
   };
@@ -469,23 +437,7 @@ split_gemm_pingpong_kernel(const WdConvGemm p, const unsigned char* __restrict__
   const int mw = m0 + group * 128 + wm * 64, nw = n0 + wn * 32 * TN;
   float* patch = reinterpret_cast<float*>(smem_raw) + wave * 32 * EPI_LDT;
   static_assert(NBUF * STAGE >= 8 * 32 * EPI_LDT * 4, "operand LDS must hold one patch per wave");
-  if (VAR & SVAR_CSPLIT) {
-    switch (p.act) {
-      case WD_ACT_RELU: EpiCsplitWalk<0, TM, TN, WD_ACT_RELU>::run(p, ev, mw, nw, lane, acc, patch); break;
-      case WD_ACT_SILU: EpiCsplitWalk<0, TM, TN, WD_ACT_SILU>::run(p, ev, mw, nw, lane, acc, patch); break;
-      case WD_ACT_GELU: EpiCsplitWalk<0, TM, TN, WD_ACT_GELU>::run(p, ev, mw, nw, lane, acc, patch); break;
-      default: EpiCsplitWalk<0, TM, TN, WD_ACT_NONE>::run(p, ev, mw, nw, lane, acc, patch); break;
-    }
-  } else if (epi_res_prefetch_ok(p, ev, nw, TN * 32) && mw < p.m) {
-    split_epilogue_res_prefetch<TM, TN, EPI_RES_DEPTH>(p, ev, mw, nw, lane, acc, patch);
-  } else {
-    switch (p.act) {
-      case WD_ACT_RELU: split_epilogue_lds<TM, TN, WD_ACT_RELU, false>(p, ev, mw, nw, lane, acc, patch); break;
-      case WD_ACT_SILU: split_epilogue_lds<TM, TN, WD_ACT_SILU, false>(p, ev, mw, nw, lane, acc, patch); break;
-      case WD_ACT_GELU: split_epilogue_lds<TM, TN, WD_ACT_GELU, false>(p, ev, mw, nw, lane, acc, patch); break;
-      default: split_epilogue_lds<TM, TN, WD_ACT_NONE, false>(p, ev, mw, nw, lane, acc, patch); break;
-    }
-  }
+  split_store_tail<TM, TN, EPI_RES_DEPTH, (VAR & SVAR_CSPLIT) != 0>(p, ev, mw, nw, TN * 32, lane, acc, patch);
 }
 
 template <int VAR, int NBUF, int TN>
@@ -495,16 +447,14 @@ int launch_pingpong(const WdConvGemm& p, const void* wsp, float unscale, hipStre
   const long long nblk = (long long)nbm * nbn;
   if (nblk <= 0 || nblk > 0x7fffffffLL) return WD_ERR_BAD_ARG;
   const int k16 = (p.k + 15) / 16 * 16;
-  const int vec_c = (p.ldc % 4 == 0) && wd_aligned16(p.c);
-  const int vec_res = p.res ? ((p.ldres % 4 == 0) && wd_aligned16(p.res)) : 0;
-  const int vec_bias = p.bias ? wd_aligned16(p.bias) : 0;
+  const WdEpiVecFlags vf = wd_epi_vec_flags(p, false);
   const float* zero = wd_zero_block();
   if (!zero) return WD_ERR_LAUNCH;
   auto k = split_gemm_pingpong_kernel<VAR, NBUF, TN>;
   static WdAttrOnce attr;
   if (wd_set_max_lds(attr, reinterpret_cast<const void*>(k), LDS) != WD_OK) return WD_ERR_LAUNCH;
   WD_LAUNCH_GEMM(k, dim3((unsigned)nblk), dim3(512), LDS, st, p, static_cast<const unsigned char*>(wsp), zero, k16,
-                     unscale, nbn, vec_c, vec_res, vec_bias, ra);
+                     unscale, nbn, vf.c, vf.res, vf.bias, ra);
   return wd_launch_status();
 }
 
