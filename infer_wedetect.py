@@ -101,6 +101,9 @@ def parse_args(argv=None):
     parser.add_argument("--track-w-iou", default=0.5, type=float, help="with --track: weight of the IoU against the appearance term, 0 .. 1")
     parser.add_argument("--track-max-age", default=30, type=int, help="with --track: frames a track survives unmatched")
     parser.add_argument("--track-labels", action="store_true", help="with --track: a match needs equal labels")
+    parser.add_argument("--track-assign", default="greedy", choices=("greedy", "optimal"),
+                        help="with --track: how a round associates detections with tracks: the greedy picks, or the "
+                             "maximum-weight (Hungarian) matching solved on the device")
     args = parser.parse_args(argv)
     args.exemplars = None
     if not args.track and any(a.startswith("--track-") for a in (sys.argv[1:] if argv is None else argv)):
@@ -163,7 +166,8 @@ def tracked_detections(model, images, texts, test_pipeline, args):
     params = track_params(args)
     for i in range(0, len(images), args.track_batch):
         infos = [test_pipeline(dict(img_id=i + k, img_path=p, texts=texts)) for k, p in enumerate(images[i:i + args.track_batch])]
-        outs = model.track(torch.stack([d["inputs"] for d in infos]), [d["data_samples"] for d in infos], n_seq=1, track_params=params)
+        outs = model.track(torch.stack([d["inputs"] for d in infos]), [d["data_samples"] for d in infos], n_seq=1, track_params=params,
+                           assignment=args.track_assign)
         for o in outs:
             pred = o.pred_instances
             pred = pred[pred.scores.float() > args.threshold]

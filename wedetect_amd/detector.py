@@ -1050,13 +1050,16 @@ class YOLOWorldDetector(_DeviceModule):
 
     # -- tracking ----------------------------------------------------------------------------
     @torch.no_grad()
-    def track(self, batch_inputs, batch_data_samples, rescale: bool = True, n_seq: int = 1, tracker=None, track_params=None):
+    def track(self, batch_inputs, batch_data_samples, rescale: bool = True, n_seq: int = 1, tracker=None, track_params=None,
+              assignment=None):
         """``predict`` for the frames of a video, plus persistent ids: ``pred_instances`` gains ``track_ids`` (int32, 0 = the
         detection belongs to no track) and ``track_hits`` (frames the track was matched in), on the device like the other fields.
         The batch holds ``n_seq`` independent sequences of ``len(batch) / n_seq`` consecutive frames each, image s * n_frame + f
         being frame f of sequence s: one video -> ``n_seq=1``, one frame of each of B cameras -> ``n_seq=B``.  The tracks live in
         ``tracker`` (a ``track.Tracker``; the detector makes and keeps one, with ``track_params`` — a ``track.TrackParams`` — on
-        the first call) and carry over from call to call; ``reset_tracks()`` clears them.
+        the first call) and carry over from call to call; ``reset_tracks()`` clears them.  ``assignment`` ("greedy", the default,
+        or "optimal": the maximum-weight matching of include/addons/wedetect_hip_assign.h in place of the greedy picks) goes to the
+        tracker the detector makes and must not differ from the kept one's; with a ``tracker`` passed in it must be None.
 
         The association (include/wedetect_hip_track.h: two greedy rounds on IoU and the kept rows' region embeddings) is ONE
         launch behind the tower step, with no host synchronisation of its own: the step runs with ``with_embed=True`` under the
@@ -1072,7 +1075,12 @@ class YOLOWorldDetector(_DeviceModule):
         n = len(batch_inputs)
         if isinstance(n_seq, bool) or not isinstance(n_seq, int) or n_seq < 1 or n % n_seq:
             raise ValueError(f"n_seq must be a positive int that divides the batch of {n} images, got {n_seq!r}")
+        if assignment is not None and assignment not in T.ASSIGNMENTS:
+            raise ValueError(f"assignment: one of {T.ASSIGNMENTS} or None is expected, got {assignment!r}")
         if tracker is None:
+            if self._tracker is not None and assignment is not None and assignment != self._tracker.assignment:
+                raise ValueError(f"assignment {assignment!r} differs from that of the detector's tracker "
+                                 f"({self._tracker.assignment!r}): call reset_tracks() first")
             if self._tracker is not None and self._tracker.n_seq != n_seq:
                 raise ValueError(f"the detector's tracker holds {self._tracker.n_seq} sequences, this call has {n_seq}: call "
                                  "reset_tracks() first, or pass a tracker")
@@ -1082,10 +1090,13 @@ class YOLOWorldDetector(_DeviceModule):
             raise ValueError(f"tracker must be a track.Tracker of {n_seq} sequences and dim {EMBED_DIM}")
         elif track_params is not None:
             raise ValueError("track_params belong to the detector's own tracker: a tracker that is passed in carries its own")
+        elif assignment is not None:
+            raise ValueError("assignment belongs to the detector's own tracker: a tracker that is passed in carries its own")
         res, counts, samples = self._predict_step(batch_inputs, batch_data_samples, rescale, with_embed=True)
         if tracker is None:
             if self._tracker is None:
-                self._tracker = T.Tracker(n_seq, dim=EMBED_DIM, params=track_params, device=self._h.device)
+                self._tracker = T.Tracker(n_seq, dim=EMBED_DIM, params=track_params, device=self._h.device,
+                                          assignment=assignment or "greedy")
             tracker = self._tracker
         ids, hits = tracker.update(res, n // n_seq)
         return self._instances(res, counts, samples, (("track_ids", ids), ("track_hits", hits)))

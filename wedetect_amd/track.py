@@ -20,6 +20,7 @@ MAX_OUT = 1024                   # WD_TRACK_MAX_OUT
 MAX_DIM = 1024                   # WD_TRACK_MAX_DIM
 STATUS_FULL = 1                  # WD_TRACK_STATUS_FULL
 STATUS_BAD_COUNT = 2             # WD_TRACK_STATUS_BAD_COUNT
+ASSIGNMENTS = ("greedy", "optimal")   # Tracker(assignment=...): wd_track_step / wd_track_step_optimal (wedetect_amd/assign.py)
 
 SIGNATURES = {
     "wd_track_abi_version": (None, []),
@@ -127,8 +128,16 @@ class Tracker:
     ``update`` is one launch on the current stream and never synchronises; the tensors it returns are overwritten by the next
     call."""
 
-    def __init__(self, n_seq: int = 1, max_tracks: int = 128, dim: int = 768, params: Optional[TrackParams] = None, device=None):
+    def __init__(self, n_seq: int = 1, max_tracks: int = 128, dim: int = 768, params: Optional[TrackParams] = None, device=None, *,
+                 assignment: str = "greedy"):
         check_sizes(n_seq, max_tracks, dim)
+        if assignment not in ASSIGNMENTS:
+            raise ValueError(f"assignment: one of {ASSIGNMENTS} is expected, got {assignment!r}")
+        self.assignment = assignment                      # fixed for the tracker's life
+        self._assign = None
+        if assignment == "optimal":                       # the add-on binding is loaded only when it is asked for
+            from . import assign as _assign
+            self._assign = _assign
         self.n_seq, self.max_tracks, self.dim = n_seq, max_tracks, dim
         self.params = params if params is not None else TrackParams()
         if not isinstance(self.params, TrackParams):
@@ -180,16 +189,18 @@ class Tracker:
                 raise ValueError(f"{name}: a contiguous {dt} tensor {shape} on {self.device} is expected, got {t.dtype} "
                                  f"{tuple(t.shape)} on {t.device}")
         if self._ws is None or max_out > self._ws_out:
-            self._ws = torch.empty(workspace_bytes(self.n_seq, self.max_tracks, max_out), dtype=torch.uint8, device=self.device)
+            size = workspace_bytes if self._assign is None else self._assign.track_optimal_workspace_bytes
+            self._ws = torch.empty(size(self.n_seq, self.max_tracks, max_out), dtype=torch.uint8, device=self.device)
             self._ws_out = max_out
         out = self._out.get((n_img, max_out))
         if out is None:
             self._out.clear()
             out = self._out[(n_img, max_out)] = (torch.empty(n_img, max_out, dtype=torch.int32, device=self.device),
                                                 torch.empty(n_img, max_out, dtype=torch.int32, device=self.device))
+        step = track_step if self._assign is None else self._assign.track_step_optimal
         with torch.cuda.device(self.device):
-            track_step(self.state, self._ws, boxes, scores, labels, count, embed, self.n_seq, n_frame, max_out, self.max_tracks,
-                       self.dim, self._struct, out[0], out[1])
+            step(self.state, self._ws, boxes, scores, labels, count, embed, self.n_seq, n_frame, max_out, self.max_tracks,
+                 self.dim, self._struct, out[0], out[1])
         return out
 
     def tracks(self, with_embed: bool = False) -> List[dict]:
